@@ -11,10 +11,20 @@ own 4096-sample batches: the path partitions by sample with no data-path collect
 so scaling is weak and the value is all ranks' samples / max-over-ranks time.  The
 N = 1 output is unchanged by the launcher (no process group, no hand-off).
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps,
+writes the last step's outputs if ``--dump-outputs DIR`` is given, and prints the line;
+every record below ``roofline`` is null in it.  ``--full`` adds those records (runs of
+their own after the timed steps; each keeps its own opt-out option) and the one-launch
+bracket behind the roofline's marginal per-launch time.
+
 Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md §6):
   value            samples/s, whole job
+  ms_per_step      wall-clock milliseconds per timed step (max over ranks)
   roofline         HBM roofline of the fused kernel from live HIP-event timing (hot
-                   Infinity Cache: back-to-back launches); ``cache_cold`` repeats it
+                   Infinity Cache: back-to-back launches); a plain run has the raw
+                   t_K / K figure, ``--full`` the marginal one
+ --full only:
+  cache_cold       the roofline repeated
                    with a 512 MiB scrub write between launches (> the 256 MiB MALL)
   cpu_baseline     the CPU oracle (reference op sequence, torch CPU) on a bounded
                    sample: all usable cores + 1 thread, forward and forward+backward
@@ -66,6 +76,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other record (one-launch "
+                         "bracket, sweep, multistream, cold cache, forward + backward, config 5, "
+                         "training step, CPU baseline); each keeps its own opt-out option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed on rank 0 "
+                         "(out, angles) as DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--lmax", type=int, default=10)
     ap.add_argument("--channels", type=int, default=10)
@@ -96,7 +113,33 @@ def parse():
                     help="A/B only: time the instantiation without the angles output")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the rank plumbing on CPU (gloo, no HIP call)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write the tensors of ``arrays`` (name -> tensor, first axis = sample) as
+    ``path/<name>.npy`` in float32.  All of them whole when that fits DUMP_MAX_BYTES in all;
+    otherwise the same fixed sample of rows of each (a seeded draw without replacement, in
+    ascending order), as many rows as fit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values())
+    keep = None
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        n = max(1, DUMP_MAX_BYTES // row_bytes)
+        g = torch.Generator(device="cpu").manual_seed(64)
+        keep = torch.randperm(rows, generator=g)[:n].sort().values
+    for name, t in arrays.items():
+        if keep is not None:
+            t = t.index_select(0, keep.to(t.device))
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def algorithmic_bytes(batch, L, C, out_bytes):
@@ -341,6 +384,14 @@ def main():
     wall_max = launch.max_over_ranks(wall, dev)
     nranks = launch.ranks_seen(dev)  # after the timed region: ranks the collective reached
 
+    if args.dump_outputs and rank == 0:
+        # before any further launch: what the last timed step left in its output buffers
+        # (rank 0's batch; the other ranks run the same path on their own seeds)
+        arrays = {"out": out}
+        if not args.no_ang:
+            arrays["angles"] = ang_buf
+        dump_outputs(args.dump_outputs, arrays)
+
     value = B * args.steps * world / wall_max
     # The events around the timed region also hold a fixed cost that does not scale with
     # K: the first kernel's start after the idle, synchronised GPU (the host's submission
@@ -350,7 +401,7 @@ def main():
     # the per-launch figure is the marginal (t_K - t_1) / (K - 1); the raw t_K / K is kept.
     raw_per_launch_s = gpu_ms / 1e3 / args.steps
     per_launch_s, t1_us = raw_per_launch_s, None
-    if args.steps >= 10:
+    if args.full and args.steps >= 10:
         # t_1 is bracketed exactly as t_K was: stream events around one replay, or (with
         # --events-in-graph) event nodes inside a one-launch graph
         if args.launch == "graph" and events_in_graph:
@@ -383,7 +434,7 @@ def main():
 
     sweep = None
     sweep_batches = [int(b) for b in args.sweep.split(",") if b.strip()]
-    if sweep_batches and rank == 0:
+    if args.full and sweep_batches and rank == 0:
         sweep = []
         for nb in sweep_batches:
             vv = torch.randn(nb, 3, device=dev)
@@ -409,7 +460,7 @@ def main():
 
     # independent batches on parallel streams (same kernel): aggregate throughput
     multi = None
-    if args.launch == "graph" and args.multistream > 1:
+    if args.full and args.launch == "graph" and args.multistream > 1:
         ms = args.multistream
         mouts = [torch.empty(B, M, C, device=dev, dtype=out_dtype) for _ in range(ms)]
         mangs = [torch.empty(B, 3, device=dev) for _ in range(ms)]
@@ -439,10 +490,12 @@ def main():
                  "aggregate_GBs": abytes * reps * mchunk / el2 / 1e9}
         del mouts, mangs
 
-    cache_cold = cold(args.cold_launches) if args.cold_launches > 0 and rank == 0 else None
+    cache_cold = None
+    if args.full and args.cold_launches > 0 and rank == 0:
+        cache_cold = cold(args.cold_launches)
 
     fwd_bwd = None
-    if not args.no_fwd_bwd and rank == 0 and args.dtype == "f32":
+    if args.full and not args.no_fwd_bwd and rank == 0 and args.dtype == "f32":
         fwd_bwd = bench_fwd_bwd(v, F, L, dev, stream)
 
     # HBM traffic per launch is NOT measured in this run (PMC counters need their own
@@ -462,17 +515,17 @@ def main():
     # BASELINE configs 5 and 3 / 4 as bounded sub-records of the same line (every rank
     # takes part: they are timed max over ranks like the headline)
     config5 = None
-    if args.config5_launches > 0:
+    if args.full and args.config5_launches > 0:
         config5 = bench_config5(lib, dev, stream, world, rank, args.config5_launches)
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         train = bench_train_step(dev, env, args.train_steps, args.train_warmup)
 
     # the CPU baseline last: ~18 s of all-thread host work right before the host-bound
     # bf16 training step slowed that step 1.2-2.7x on the driver's box (3.9-4.3 ms per step
     # without it in the same bench, 4.8-10.6 ms after it)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(L, C, B, args.cpu_seconds)
 
     if rank == 0:
@@ -485,6 +538,7 @@ def main():
             "max_over_ranks": world > 1,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": wall_max * 1e3 / args.steps,
             "higher_is_better": True,
             "scaling": "weak",
@@ -503,7 +557,10 @@ def main():
                          "us_per_launch_events": per_launch_s * 1e6,
                          "us_per_launch_events_raw": raw_per_launch_s * 1e6,
                          "us_one_launch_bracket": t1_us,
-                         "per_launch_rule": "MARGINAL per-launch time (t_K - t_1) / (K - 1): "
+                         "per_launch_rule": "raw t_K / K: HIP events bracket the K timed launches "
+                                            "(the marginal figure needs --full and K >= 10)"
+                                            if t1_us is None else  # else: the --full rule
+                                            "MARGINAL per-launch time (t_K - t_1) / (K - 1): "
                                             "HIP events bracket the K timed launches and, the "
                                             "same way, one launch (median of 5); the fixed "
                                             "submission cost both brackets hold cancels. The "

@@ -59,19 +59,19 @@ for s in "$@"; do
     smoke)
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; tail -1 "$OUT/smoke.log" ;;
     driver)
-      step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5; summary "$OUT/bench_driver.log" ;;
+      step bench_driver 300 python bench.py --full --gpus 1 --steps 20 --warmup 5; summary "$OUT/bench_driver.log" ;;
     c5)
-      step bench_c5 600 python bench.py --lmax 20 --batch 8192 --dtype bf16 --no-cpu-baseline --steps 500 --sweep ""
+      step bench_c5 600 python bench.py --full --lmax 20 --batch 8192 --dtype bf16 --no-cpu-baseline --steps 500 --sweep ""
       summary "$OUT/bench_c5.log" ;;
     sweep)
-      step bench_sweep 600 python bench.py --no-cpu-baseline --sweep 16384,65536,262144 --no-fwd-bwd
+      step bench_sweep 600 python bench.py --full --no-cpu-baseline --sweep 16384,65536,262144 --no-fwd-bwd
       summary "$OUT/bench_sweep.log" ;;
     prof-c2)
       step prof_c2 900 bash tools/gpu_prof.sh c2 --batch 4096 --lmax 10 --dtype f32 ;;
     prof-c5)
       step prof_c5 900 bash tools/gpu_prof.sh c5 --batch 8192 --lmax 20 --dtype bf16 ;;
     prof-driver)
-      step rocprof_driver 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_driver" -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5
+      step rocprof_driver 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_driver" -o run --output-format csv -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5
       rm -f "$OUT"/prof_driver/*kernel_trace.csv ;;
     train)
       step train_bf16 600 python bench_train.py --global-batch 512 --steps 30 --amp bf16 --channels-last

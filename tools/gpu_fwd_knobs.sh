@@ -9,7 +9,7 @@ mkdir -p gpurun_out/fwd_knobs
 export LIEVAE_HIP_LIB=$PWD/lie-vae_amd/lie_vae/liblievae_hip_ab.so
 run() {  # tag, env...
   local tag=$1; shift
-  env "$@" timeout -k 10 240 python bench.py --steps 400 --warmup 50 --no-fwd-bwd --no-cpu-baseline \
+  env "$@" timeout -k 10 240 python bench.py --full --steps 400 --warmup 50 --no-fwd-bwd --no-cpu-baseline \
       --cold-launches 0 --sweep 16384,65536,262144 > gpurun_out/fwd_knobs/$tag.log 2>&1 || { echo "$tag failed"; tail -3 gpurun_out/fwd_knobs/$tag.log; exit 1; }
   python3 - "$tag" gpurun_out/fwd_knobs/$tag.log <<'PY'
 import json, sys
@@ -25,7 +25,7 @@ run base2
 # config 5 (l = 20, B = 8192, bf16 out): one-shot tile kernel vs the persistent one
 run_c5() {
   local tag=$1; shift
-  env "$@" timeout -k 10 240 python bench.py --lmax 20 --batch 8192 --dtype bf16 --steps 300 --warmup 30 --no-fwd-bwd \
+  env "$@" timeout -k 10 240 python bench.py --full --lmax 20 --batch 8192 --dtype bf16 --steps 300 --warmup 30 --no-fwd-bwd \
       --no-cpu-baseline --cold-launches 0 --multistream 1 --sweep 65536 > gpurun_out/fwd_knobs/$tag.log 2>&1 || { echo "$tag failed"; tail -3 gpurun_out/fwd_knobs/$tag.log; exit 1; }
   python3 - "$tag" gpurun_out/fwd_knobs/$tag.log <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # forward at 4,096 + sweep, config 5.  Usage: bash tools/gpu_libs_ab.sh lib1.so lib2.so ...
 set -u
 cd "$(dirname "$0")/.."
-B="--train-steps 0 --no-fwd-bwd --no-cpu-baseline --cold-launches 0 --multistream 1 --steps 400 --warmup 40 --config5-launches 200"
+B="--full --train-steps 0 --no-fwd-bwd --no-cpu-baseline --cold-launches 0 --multistream 1 --steps 400 --warmup 40 --config5-launches 200"
 for r in 1 2; do
 for lib in "$@"; do
   export LIEVAE_HIP_LIB=$PWD/lie-vae_amd/lie_vae/$lib
