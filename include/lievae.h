@@ -64,7 +64,10 @@ int lv_so3_sample_bwd(const float* mu, const float* v, const float* gz, float* g
 /* ---- backward of z = mu @ exp(v) -> group_matrix_to_eazyz(z) in one pass ----
  * reparameterize.py:269-273 -> vae.py:182 (the fused path's prologue).  mu may be NULL
  * (z = exp(v)); then gmu is not written.  gang (n,3) -> gv (n,3), gmu (n,3,3).
- * Bitwise the same as lv_so3_exp_fwd / lv_mat_to_eazyz_bwd / lv_so3_exp_bwd in turn. */
+ * The chain runs in fp64 on the fp32 inputs and is rounded once (in fp32 it loses up to
+ * ~1e-3 of a sample's gradient near beta = 0 / pi): bitwise lv_so3_exp_fwd_f64 /
+ * lv_mat_to_eazyz_bwd_f64 / lv_so3_exp_bwd_f64 in turn on the inputs cast up, rounded to
+ * fp32. */
 int lv_exp_eazyz_vjp(const float* mu, const float* v, const float* gang, float* gmu, float* gv,
                      int64_t n, void* stream);
 
@@ -179,7 +182,9 @@ int lv_group_action_bwd(const float* ang, const float* F, int64_t F_batch_stride
 /* ---- fused metric kernel: z = mu @ rodrigues(v) -> ZYZ -> block D(z)·F ------
  * reparameterize.py:269-273 + vae.py:182 + decoders.py:47-56 in one pass.
  * mu (n,3,3) or NULL (identity); v (n,3); optional ang_out (n,3) receives the
- * Euler angles (for the backward).  Other arguments as lv_group_action_fwd. */
+ * Euler angles (for the backward; beta = atan2(sin, cos) of the pair D is evaluated with,
+ * accurate near 0 / pi where acos of an fp32 cosine is not).  Other arguments as
+ * lv_group_action_fwd. */
 int lv_fused_exp_action_fwd(const float* mu, const float* v, const float* F,
                             int64_t F_batch_stride, void* out, int out_dtype, float* ang_out,
                             int64_t n, int L, int C, int transpose, void* stream);

@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void action_bwd_reduce5_kernel(const float* ws
 }
 
 // The persistent backward's fused tail in one launch: blocks [0, nvjp) run the exp -> ZYZ
-// VJP (exp_eazyz_vjp_sample, one sample per thread: the same per-sample function as
+// VJP (exp_eazyz_vjp_sample_wide, one sample per thread: the same per-sample function as
 // lv_exp_eazyz_vjp, so the same bits), blocks [nvjp, nvjp + chunks) the reduce5 dF sum.
 // Both read only the persistent kernel's outputs, so they run side by side instead of
 // back to back (the VJP is one long dependent chain per sample at one wave per SIMD).
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void action_bwd_reduce5_vjp_kernel(const float
 #pragma unroll
         for (int k = 0; k < 9; ++k) m[k] = mu[i * 9 + k];
       }
-      exp_eazyz_vjp_sample(av, mu != nullptr, m, g, gm, o);
+      exp_eazyz_vjp_sample_wide(av, mu != nullptr, m, g, gm, o);
       if (mu) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) gmu[i * 9 + k] = gm[k];

@@ -163,6 +163,12 @@ __device__ __forceinline__ void exp_beta(const ExpQuat& e, float& c, float& s) {
   c = omc <= opc ? 1.f - omc : opc - 1.f;
   s = __builtin_amdgcn_sqrtf(omc * opc);  // v_sqrt_f32 (1 ulp)
 }
+// beta as the fused forward saves it for the backward (ang_out): from the (cos, sin) pair
+// the forward itself evaluates D with, whose sine keeps its relative accuracy near beta = 0 /
+// pi.  acos of an fp32 cos(beta), as quat_to_eazyz_fwd (the reference's formula) takes it,
+// is off by ~6e-8 / sin(beta) per ulp of the cosine -- 1.7e-5 at beta = 0.009 -- and the
+// backward, evaluated at that beta, by ~1e-3 of the sample's gradient.
+__device__ __forceinline__ float saved_beta(float cb, float sb) { return atan2f(sb, cb); }
 // (cos, sin) of alpha (ai = 0) or gamma (ai = 2): the direction of (x, y), atan2(+-0, +-0)
 // in {0, +-pi} mirrored
 __device__ __forceinline__ void exp_dir(const ExpQuat& e, int ai, float& c, float& s) {
@@ -316,6 +322,7 @@ __device__ __forceinline__ void lane_angles(const ActionArgs& a, const LaneIn& i
     if (write_ang && active && c == 0) {
       float ang[3];
       quat_to_eazyz_fwd(q, ang);
+      ang[1] = saved_beta(cc[1], ss[1]);
       a.ang_out[s * 3 + 0] = ang[0];
       a.ang_out[s * 3 + 1] = ang[1];
       a.ang_out[s * 3 + 2] = ang[2];

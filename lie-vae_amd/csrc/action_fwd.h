@@ -314,25 +314,38 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   LaneIn in;
   if (task) lane_load<FUSED, MAYMU>(a, st, in);
   // The mu-free fused kernel writes ang_out (the product operator's saved angles) from
-  // wave 1, lanes j < Sv, during the prologue -- a wave that only stages spectrum rows
-  // there, on another SIMD than the task lanes of wave 0 -- instead of on the q = 0 task
+  // waves 1 and 2, lanes j < Sv, during the prologue -- waves that only stage spectrum rows
+  // there, on other SIMDs than the task lanes of wave 0 -- instead of on the q = 0 task
   // lanes, where quat_to_eazyz_fwd's atan2 / acos held wave 0's multiples by ~0.5 us per
-  // launch.  Same quaternion (exp_quat), so the same angles bit for bit.  (A one-wave
-  // block writes them after its chain.)
+  // launch.  Same quaternion (exp_quat), so the same angles bit for bit.  Wave 1 writes
+  // alpha and gamma, wave 2 beta = saved_beta of the forward's own (cos, sin) pair (a
+  // longer chain than the acos it replaces: all three on wave 1 cost 0.11 us per launch at
+  // config 2, split 0.06 us); a two-wave block writes all three from wave 1, a one-wave
+  // block after its chain.
   constexpr bool kAngLate = FUSED && !MAYMU;
   const int ang_wave = (nthr >> 6) > 1 ? 1 : 0;
-  const bool ang_lane = kAngLate && a.ang_out != nullptr && wave == ang_wave && lane < Sv;
-  auto write_ang = [&]() {
+  const int beta_wave = (nthr >> 6) > 2 ? 2 : ang_wave;
+  const bool ang_on = kAngLate && a.ang_out != nullptr && lane < Sv;
+  const bool ang_lane = ang_on && wave == ang_wave;
+  const bool beta_lane = ang_on && wave == beta_wave;
+  auto write_ang = [&](bool dirs, bool beta) {
     float vang[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) vang[i] = a.v[(s0 + lane) * 3 + i];
     const ExpQuat e = exp_quat(vang);
-    float ang[3];
-    quat_to_eazyz_fwd(e.qr, ang);
-    a.ang_out[(s0 + lane) * 3 + 0] = ang[0];
-    a.ang_out[(s0 + lane) * 3 + 1] = ang[1];
-    a.ang_out[(s0 + lane) * 3 + 2] = ang[2];
+    if (dirs) {
+      float ang[3];
+      quat_to_eazyz_fwd(e.qr, ang);
+      a.ang_out[(s0 + lane) * 3 + 0] = ang[0];
+      a.ang_out[(s0 + lane) * 3 + 2] = ang[2];
+    }
+    if (beta) {
+      float cb, sb;
+      exp_beta(e, cb, sb);
+      a.ang_out[(s0 + lane) * 3 + 1] = saved_beta(cb, sb);
+    }
   };
+  const bool early_dirs = ang_lane && ang_wave == 1, early_beta = beta_lane && beta_wave >= 1;
   // a.ang_order 0 (default): wave 1 writes the angles before it issues its spectrum loads,
   // so its two global round trips run back to back and it reaches the prologue barrier last
   // (timeline at 4,096: loads landed 1.08 us after wave start vs 0.52-0.68 on the other
@@ -340,7 +353,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   // load and the spectrum loads are in flight together.  A/B at config 2: 7.15 / 7.16 us
   // for 1 against 7.14 / 7.13 for 0 (profiles/r06_ab_ang_order_c2.txt) -- the other waves'
   // chains hide the late wave, so the round-5 order stays
-  if (ang_lane && ang_wave == 1 && a.ang_order == 0) write_ang();
+  if ((early_dirs || early_beta) && a.ang_order == 0) write_ang(early_dirs, early_beta);
   // 2. spectrum staging: every load issued now (before the prologue maths), the LDS writes
   //    after it.  CT > 0: element e = tid + k * nthr of the whole (M, C) spectrum, at most
   //    kFPer per thread for the smallest block the plan makes (2 waves), a batched loop
@@ -357,7 +370,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
     const int e = fbase + fstr * k;
     fv[k] = e < fcnt ? fsrc[e] : 0.f;
   }
-  if (ang_lane && ang_wave == 1 && a.ang_order != 0) write_ang();
+  if ((early_dirs || early_beta) && a.ang_order != 0) write_ang(early_dirs, early_beta);
   if (a.stamps) {  // A/B timeline: when this wave's loads (v; spectrum) have landed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     phase_stamp(a.stamps, wave, 5);
@@ -443,7 +456,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
       if (a.stamps) degree_stamp(a.stamps, wave, l);
     }
   });
-  if (ang_lane && ang_wave == 0) write_ang();
+  if (ang_lane && ang_wave == 0) write_ang(true, true);
   phase_stamp(a.stamps, wave, 2);
   block_sync_lds();
   phase_stamp(a.stamps, wave, 3);

@@ -106,10 +106,13 @@ __global__ void so3_sample_bwd_k(const T* mu, const T* v, const T* gz, T* gmu,
 
 // Backward of the fused path's prologue, z = mu @ exp(v) (mu optional) -> ZYZ angles, in
 // one pass per sample: the composition of so3_sample_fwd/so3_exp_fwd, mat_to_eazyz_bwd
-// and so3_sample_bwd/so3_exp_bwd above (same device functions, same operation order,
-// hence bitwise the same gradients) without the three launches and the (n,3,3)
-// round trips through memory.  reparameterize.py:269-273 + vae.py:182 (autograd in the
-// reference).
+// and so3_sample_bwd/so3_exp_bwd above (same device functions, same operation order)
+// without the three launches and the (n,3,3) round trips through memory.  The fp64 entry
+// gives bitwise the gradients of the fp64 modular kernels; the fp32 entry runs the same
+// fp64 chain on its inputs cast up and rounds once (so3_device.h
+// exp_eazyz_vjp_sample_wide: the fp32 chain loses up to ~1e-3 of a sample's gradient near
+// beta = 0 / pi), i.e. the fp64 modular kernels' gradients rounded to fp32.
+// reparameterize.py:269-273 + vae.py:182 (autograd in the reference).
 template <typename T>
 __global__ void exp_eazyz_vjp_k(const T* mu, const T* v, const T* ga, T* gmu,
                                 T* gv, int64_t n) {
@@ -118,7 +121,9 @@ __global__ void exp_eazyz_vjp_k(const T* mu, const T* v, const T* ga, T* gmu,
     ld(v + i * 3, a);
     ld(ga + i * 3, g);
     if (mu) ld(mu + i * 9, m);
-    exp_eazyz_vjp_sample(a, mu != nullptr, m, g, gm, o);
+    // fp32: the chain in fp64, rounded once (exp_eazyz_vjp_sample_wide)
+    if constexpr (std::is_same_v<T, float>) exp_eazyz_vjp_sample_wide(a, mu != nullptr, m, g, gm, o);
+    else exp_eazyz_vjp_sample(a, mu != nullptr, m, g, gm, o);
     if (mu) st(gmu + i * 9, gm);
     st(gv + i * 3, o);
   }

@@ -351,6 +351,30 @@ __device__ __forceinline__ void exp_eazyz_vjp_sample(const T a[3], bool has_m, c
   }
 }
 
+// The fp32 entry points' VJP: fp32 in and out, the chain itself in fp64, rounded once.  Near
+// beta = 0 / pi the chain is ill-conditioned in fp32 -- r1 = a1^2 + b1^2 -> 0 in
+// quat_to_eazyz_bwd, and the angle gradients g[0], g[2] cancel to O(beta) -- so its own
+// rounding costs up to ~1e-3 of a sample's gradient at beta ~ 1e-2 (as the reference's fp32
+// autograd does there); in fp64 every sample stays within ~3e-5 of the fp64 autograd, what
+// remains being the fp32 rounding of g.  One dependent chain per sample either way.
+__device__ __forceinline__ void exp_eazyz_vjp_sample_wide(const float a[3], bool has_m, const float m[9],
+                                                          const float g[3], float gm[9], float gv[3]) {
+  double ad[3], gd[3], md[9], gmd[9], gvd[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { ad[k] = a[k]; gd[k] = g[k]; }
+  if (has_m) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) md[k] = m[k];
+  }
+  exp_eazyz_vjp_sample<double>(ad, has_m, md, gd, gmd, gvd);
+  if (has_m) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) gm[k] = (float)gmd[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) gv[k] = (float)gvd[k];
+}
+
 // ------------------------------------------------------------- s2s1rodrigues
 // lie_tools.py:67-78: R = I + sin K + (1 - cos) K@K, K = hat(axis), (cos, sin) given.
 template <typename T>

@@ -137,6 +137,62 @@ def test_pinned_plans_of_the_benchmark_configs():
     assert _lib.plan("bwd", 4096, 20, 13, 1)["tile"] == 1
 
 
+def test_action_matrix_case_table_reaches_every_branch():
+    """The case table of tests/test_gpu_action_matrix.py (tests/action_matrix_cases.py),
+    classified by the dispatch branch each run reaches -- forward: tile / grid-stride x C = 10
+    / run-time C x spectrum and trig tables below / from l = 13 x fp32 / bf16 x angles / fused
+    with / without a mean; backward: plan mode 0-3 x C = 10 / run-time C x one group per block
+    / looped x full / reduced samples per group.  Every value of every dimension, the
+    branches the table was built for, every branch the planner reaches anywhere in its
+    domain, and every l_max forward and backward are hit by at least one case: a planner
+    change that moves the cases off a branch fails here instead of emptying the GPU test."""
+    import action_matrix_cases as amc
+    fwd, bwd = amc.table_branches()
+    for k, values in enumerate((("tile", "grid"), ("c10", "crt"), ("l<13", "l>=13"), ("f32", "bf16"),
+                                ("angles", "fused_mu", "fused_nomu"))):
+        assert {b[k] for b in fwd} == set(values), (k, values)
+    for k, values in enumerate(((0, 1, 2, 3), ("c10", "crt"), ("one", "looped"), ("full", "reduced"))):
+        assert {b[k] for b in bwd} == set(values), (k, values)
+    built_for = {
+        "fwd": [("grid", "crt", "l>=13", "f32", "fused_mu"),      # l = 20 fp32: grid-stride fused
+                ("grid", "crt", "l>=13", "f32", "fused_nomu"),
+                ("tile", "c10", "l<13", "f32", "fused_nomu"),     # the mu == NULL instantiation
+                ("tile", "c10", "l>=13", "bf16", "fused_nomu"),
+                ("tile", "crt", "l<13", "f32", "angles"),         # both sides of l = 13, run-time C
+                ("tile", "crt", "l>=13", "f32", "angles"),
+                ("tile", "crt", "l<13", "bf16", "fused_mu"),
+                ("tile", "crt", "l>=13", "bf16", "fused_mu"),
+                ("grid", "crt", "l<13", "f32", "angles")],        # per-sample spectrum
+        "bwd": [(3, "c10", "one", "full"), (3, "c10", "looped", "full"),
+                (1, "c10", "one", "reduced"), (1, "c10", "looped", "full"),
+                (1, "c10", "looped", "reduced"), (1, "crt", "looped", "full"),
+                (1, "crt", "one", "reduced"), (2, "crt", "looped", "full"),
+                (0, "crt", "one", "full"), (0, "crt", "looped", "full")],
+    }
+    assert not [b for b in built_for["fwd"] if b not in fwd]
+    assert not [b for b in built_for["bwd"] if b not in bwd]
+    reach_fwd, reach_bwd = amc.reachable_branches()
+    assert not sorted(reach_fwd - set(fwd)), "forward branches no case reaches"
+    assert not sorted(reach_bwd - set(bwd)), "backward branches no case reaches"
+    for L in range(21):
+        assert any(c.L == L for cs in fwd.values() for c in cs), f"no forward case at l = {L}"
+        assert any(c.L == L for cs in bwd.values() for c in cs), f"no backward case at l = {L}"
+    # what the sections rely on, from the planner: the persistent kernel from l = 3 at
+    # 6 (CUs + 1) + 5 samples, its degrees 3..9 and a looping grid at l != 10; every looped
+    # case's grid below its groups; reduced groups from l = 16 at C = 10
+    assert amc.PERSIST_N == 6 * (CUS + 1) + 5
+    for case in amc.PERSIST:
+        assert amc.bwd_plan(case, amc.runs(case)[0])["tile"] == (3 if case.L >= 3 else 1), case
+    assert {c.L for c in amc.PERSIST if c.L >= 3} == set(range(3, 10))
+    for case in amc.LOOPED:
+        p = amc.bwd_plan(case, amc.runs(case)[0])
+        assert p["blocks"] < amc.bwd_groups(case, p), case
+    for case in amc.DEGREE_SWEEP:
+        spg = amc.bwd_plan(case, amc.runs(case)[0])["samples_per_group"]
+        assert (spg == 6) if case.L <= 15 else (1 <= spg < 6), case
+    assert len({amc.seed(c) for c in amc.ALL_CASES}) == len({c[1:4] for c in amc.ALL_CASES})
+
+
 @pytest.mark.parametrize("args", [
     ("fwd", 1, 0, F32, 16, 21, 10),           # l_max > 20
     ("fwd", 1, 0, F32, 16, 10, 0),            # C < 1
