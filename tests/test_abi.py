@@ -179,3 +179,86 @@ def test_deconv_f32_argument_checks_before_any_launch():
     assert b"twin" in lib.lv_last_error()
     assert fwd(P, P, None, P, None, 2, 4, 4, 200, 200, 2, None) == -1  # unknown flag
     assert fwd(P, P, None, P, None, 0, 4, 4, 200, 200, 0, None) == 0   # empty batch
+
+
+def test_conv_layer_size_queries_match_closed_forms():
+    """The host-side size queries of csrc/deconv.hip and csrc/bn.hip against their closed
+    forms (tests/conv_layer_cases.py holds the constants and a transcription of bn_geom): a
+    changed tile size or block cap shows here, not as a GPU test that left its branch."""
+    import conv_layer_cases as cc
+    from lie_vae import _lib
+    lib = _lib.load()
+    for Cin in (8, 16, 24, 40, 200, 248, 256):
+        assert lib.lv_deconv4s2_packed_weight_elems(Cin) == 4 * cc.MFMA_MAX_COUT * 4 * Cin + 32
+        assert lib.lv_deconv4s2_small_packed_weight_elems(Cin) == -(-Cin // 32) * 9 * 16 * 32
+        assert lib.lv_deconv4s2_small_dgrad_weight_elems(Cin) == -(-(Cin + 1) // 16) * 16 * 160
+    shapes = [(1, 1, 1), (2, 5, 33), (3, 32, 32), (8, 2, 32), (8, 3, 32), (8, 2, 33), (cc.LOOP_N, 5, 33), (0, 5, 33)]
+    for N, H, W in shapes:
+        for Cin, Cout in ((8, 1), (40, 3), (248, 4)):
+            ntiles = N * -(-H // cc.BW_TA) * -(-W // cc.BW_TB)
+            want = (min(ntiles, cc.WG_MAX_BLOCKS) + 1) * (Cin * Cout * 16 + 4 * Cout) if N > 0 else 0
+            assert lib.lv_deconv4s2_small_bwd_workspace_elems(N, H, W, Cin, Cout) == want, (N, H, W, Cin, Cout)
+    for P in (0, 1, 255, 256, 257, 8191, 262144, 262145, 10 ** 7):
+        for C in (8, 200, 2048):
+            want = (min(cc.CS_MAX_BLOCKS, -(-P // 256)) + 1) * C if P > 0 else 0
+            assert lib.lv_channel_sum_workspace_elems(P, C) == want, (P, C)
+    for P in (0, 1, 2, 7, 8, 24, 160, 888, 904, 2560, 10400, 65536, 466040, 3276800, 10 ** 7):
+        for C in range(1, 2101):
+            geo = cc.bn_geom(P, C)
+            assert lib.lv_bn_supported(P, C) == (geo is not None), (P, C)
+            assert lib.lv_bn_workspace_elems(P, C) == cc.bn_workspace_elems(P, C), (P, C)
+    # the table's own derived sizes
+    for C, P, _ in cc.BN_GEOMETRY:  # the smallest supported P with at least 2 pixels
+        assert lib.lv_bn_supported(P, C) and not any(lib.lv_bn_supported(p, C) for p in range(2, P))
+    for C, P, nblk in cc.BN_NBLK:
+        assert cc.bn_nblk_from_workspace(lib.lv_bn_workspace_elems(P, C), C) == nblk
+
+
+def test_conv_layer_argument_checks_before_any_launch():
+    """Shapes and pointer combinations outside the conv-layer kernels' contracts return
+    LV_ERR_ARG with a message before anything is launched (dummy non-null pointers, no
+    device): channel counts, the small-Cout limits, gb without gw, gw without a workspace,
+    gx without the packed weight, an unsupported BatchNorm shape, eval mode without running
+    statistics, channel-sum widths."""
+    import ctypes
+    from lie_vae import _lib
+    lib = _lib.load()
+    P = ctypes.c_void_p(16)  # never dereferenced: the checks run first
+
+    def refused(rc, word):
+        msg = lib.lv_last_error()
+        assert rc == -1 and msg and word in msg, (rc, msg)
+
+    refused(lib.lv_deconv4s2_pack_weight_bf16(P, P, 12, 200, None), b"multiple of 8")
+    refused(lib.lv_deconv4s2_fwd_bf16_ex(P, P, None, P, 2, 4, 4, 12, 200, 0, None), b"multiple of 8")
+    for Cout in (0, 6, 212):
+        refused(lib.lv_deconv4s2_pack_weight_bf16(P, P, 200, Cout, None), b"Cout")
+        refused(lib.lv_deconv4s2_fwd_bf16_ex(P, P, None, P, 2, 4, 4, 200, Cout, 0, None), b"Cout")
+        refused(lib.lv_deconv4s2_fwd_bf16(P, P, None, P, 2, 4, 4, 200, Cout, None), b"Cout")
+    refused(lib.lv_deconv4s2_fwd_bf16_ex(P, P, None, P, 2, 4, 4, 200, 200, 2, None), b"flags")
+    # the small-Cout layer
+    refused(lib.lv_deconv4s2_small_pack_weight_bf16(P, P, 200, 5, None), b"Cout")
+    refused(lib.lv_deconv4s2_small_fwd_bf16(P, P, None, P, 2, 4, 4, 200, 5, None), b"Cout")
+    refused(lib.lv_deconv4s2_small_fwd_bf16(P, P, None, P, 2, 4, 4, 12, 3, None), b"multiple of 8")
+    refused(lib.lv_deconv4s2_small_fwd_bf16(P, P, None, P, 65536, 4, 4, 200, 3, None), b"65535")
+    refused(lib.lv_deconv4s2_small_pack_dgrad_weight_bf16(P, P, 256, 3, None), b"Cin")
+    bwd = lib.lv_deconv4s2_small_bwd_bf16_ex
+    refused(bwd(P, P, P, P, P, P, P, 2, 4, 4, 256, 3, 0, None), b"Cin")
+    refused(bwd(P, P, P, P, P, P, P, 2, 4, 4, 40, 5, 0, None), b"Cout")
+    refused(bwd(P, P, P, P, P, P, P, 2, 4, 4, 40, 3, 1, None), b"flags")
+    refused(bwd(P, P, None, None, None, P, None, 2, 4, 4, 40, 3, 0, None), b"gb")    # gb without gw
+    refused(bwd(P, P, None, None, P, None, None, 2, 4, 4, 40, 3, 0, None), b"workspace")
+    refused(bwd(P, P, None, P, None, None, None, 2, 4, 4, 40, 3, 0, None), b"weight")
+    refused(lib.lv_deconv4s2_small_bwd_bf16(P, P, None, P, None, None, None, 2, 4, 4, 40, 3, None), b"weight")
+    # BatchNorm + LeakyReLU: unsupported shapes, eval without running statistics
+    fwd, bbwd = lib.lv_bn_lrelu_fwd_bf16, lib.lv_bn_lrelu_bwd_bf16
+    for Pn, C in ((8, 4), (3, 9), (0, 8), (8, 2056 + 1)):
+        assert not lib.lv_bn_supported(Pn, C) and lib.lv_bn_workspace_elems(Pn, C) == 0
+        refused(fwd(P, P, P, P, P, 1, 0.1, 1e-5, 0.2, P, P, P, P, Pn, C, None), b"unsupported")
+        refused(bbwd(P, P, P, P, P, P, 0.2, P, P, P, P, Pn, C, None), b"unsupported")
+    refused(fwd(P, P, P, None, None, 0, 0.1, 1e-5, 0.2, P, P, P, P, 8, 8, None), b"running")
+    refused(fwd(P, P, P, P, None, 0, 0.1, 1e-5, 0.2, P, P, P, P, 8, 8, None), b"running")
+    refused(fwd(P, P, P, P, P, 1, 0.1, 1e-5, 0.2, P, None, P, P, 8, 8, None), b"save_mean")
+    # per-channel sum
+    for C in (12, 2056, 0):
+        refused(lib.lv_channel_sum_bf16(P, P, P, 100, C, None), b"multiple of 8")
