@@ -109,7 +109,7 @@ __global__ __launch_bounds__(1024) void action_bwd_reduce2_kernel(const float* w
 __global__ __launch_bounds__(1024) void action_bwd_reduce3_kernel(const float* ws_F, float* gF, int64_t MC,
                                                                   int nslab, unsigned long long* stamps) {
   typedef float f4 __attribute__((ext_vector_type(4)));
-  unsigned long long* rst = stamps ? stamps + kStampBlocks * 16 * 8 + 2 * (int64_t)blockIdx.x : nullptr;
+  unsigned long long* rst = kStamps && stamps ? stamps + kStampBlocks * 16 * 8 + 2 * (int64_t)blockIdx.x : nullptr;
   if (rst && threadIdx.x == 0) rst[0] = __builtin_amdgcn_s_memrealtime();
   __shared__ f4 part[256][4];
   const int q = (int)threadIdx.x & 3, bs = (int)threadIdx.x >> 2;
@@ -334,16 +334,29 @@ inline int plan_segments(int L, int nseg, double P, bool bwd, int* seg_lo) {
 // {5, 4} one, 7.09 vs 7.19 us, outputs bitwise identical).  At C = 10 (the only C with
 // degree sets) that is the one tile plan it changes.
 constexpr double kDegFixedFwd = 80.0, kDegFixedBwd = 30.0;
+// the forward's angle maths per wave in the same units (exp_quat + two generic atan2; exp_quat
+// + exp_beta + one atan2): ~300 / ~200 VALU instructions in the l = 10 listing at ~0.75
+// instructions per unit of degree_cost (1.06 M chain wave-instructions per launch over 683
+// blocks against a summed cost of ~2,100)
+constexpr double kAngChargeDirs = 220.0, kAngChargeBeta = 150.0;
 inline double degree_cost_sched(int l, bool bwd) {
   return (bwd ? kDegFixedBwd : kDegFixedFwd) + degree_cost(l, bwd);
 }
-inline void balance_masks(int L, int nseg, bool bwd, unsigned* masks) {
+// charge (optional): work a wave carries besides its degrees, in the same units -- the
+// forward's angle waves (kAngCharge*), which so get lighter degree sets.  Every wave gets at
+// least one degree (the kernels' plans are partitions into non-empty sets): when as many
+// degrees are left as waves are empty, they go to the empty waves.
+inline void balance_masks(int L, int nseg, bool bwd, unsigned* masks, const double* charge = nullptr) {
   double load[kMaxSeg];
-  for (int k = 0; k < nseg; ++k) { load[k] = 0.0; masks[k] = 0u; }
+  for (int k = 0; k < nseg; ++k) { load[k] = charge ? charge[k] : 0.0; masks[k] = 0u; }
+  int empty = nseg;
   for (int l = L; l >= 0; --l) {
-    int best = 0;
-    for (int k = 1; k < nseg; ++k)
-      if (load[k] < load[best]) best = k;
+    int best = -1;
+    for (int k = 0; k < nseg; ++k) {
+      if (l + 1 <= empty && masks[k] != 0u) continue;
+      if (best < 0 || load[k] < load[best]) best = k;
+    }
+    if (masks[best] == 0u) --empty;
     masks[best] |= 1u << l;
     load[best] += degree_cost_sched(l, bwd);
   }
@@ -473,9 +486,23 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   // compile-time C: cost-balanced degree sets; run-time C keeps the contiguous ranges
   // (its spectrum slices are per-wave row ranges)
   static const int kEnvContig = LV_KNOB("LV_SEG_CONTIG", 0);  // A/B: contiguous ranges everywhere
+  // where the angle waves run the ang_out maths (ActionArgs::ang_order): 0 = before their
+  // spectrum loads; A/B: 1 = behind the prologue barrier, with degree sets charged for it.
+  // Measured at config 2 on one box: 6.74-6.77 us for 1 against 6.65-6.68 for 0
+  // (profiles/r07_ab_startup_c2.txt) -- the maths leaves the start-up path but lands on the
+  // chain, which is VALU-issue bound -- so the product keeps 0.
+  static const int kEnvAngOrder = LV_KNOB("LV_TILE_ANG_ORDER", 0);
   if (a.C == kTileFastC && env_masks("LV_TILE_MASKS", L, nseg, a.seg_mask)) {
-  } else if (a.C == kTileFastC && !kEnvContig) balance_masks(L, nseg, false, a.seg_mask);
-  else contiguous_masks(a.seg_lo, nseg, a.seg_mask);
+  } else if (a.C == kTileFastC && !kEnvContig) {
+    // A/B placement 1: the fused kernel's angle waves (1: alpha and gamma, 2: beta;
+    // action_fwd.h) run that maths between the prologue barrier and their chain
+    double charge[kMaxSeg] = {};
+    if (p.fused && kEnvAngOrder != 0 && nseg > 1) {
+      charge[1] = nseg > 2 ? kAngChargeDirs : kAngChargeDirs + kAngChargeBeta;
+      if (nseg > 2) charge[2] = kAngChargeBeta;
+    }
+    balance_masks(L, nseg, false, a.seg_mask, charge);
+  } else contiguous_masks(a.seg_lo, nseg, a.seg_mask);
   // spectrum in LDS: C = kTileFastC -> the whole (M, C) once, row-major; other C ->
   // per-wave column-major slices below kTileFGlobalMinL, global memory from there
   int fp = 0;
@@ -493,7 +520,6 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   a.prio = kEnvPrio;
   static const int kEnvSpread = LV_KNOB("LV_TILE_SPREAD", 0);  // A/B: prologue tasks over all waves
   a.task_spread = kEnvSpread;
-  static const int kEnvAngOrder = LV_KNOB("LV_TILE_ANG_ORDER", 0);  // A/B: 1 = angles after the spectrum loads
   a.ang_order = kEnvAngOrder;
   p.tile = true;
   p.lds = lds;

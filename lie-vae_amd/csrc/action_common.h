@@ -4,6 +4,7 @@
 // Forward kernels: action_fwd.h; backward: action_bwd.h; host planning: action.hip.
 #include "action_chain.h"
 #include "so3_device.h"
+#include <cstddef>
 
 namespace lv {
 
@@ -13,45 +14,71 @@ constexpr int kMaxSeg = 16;
 constexpr int kTrigLdsMinL = 13;  // action_fwd_kernel keeps its trig table in LDS from here
 constexpr int kTileFGlobalMinL = 13;  // the tile kernel reads the spectrum from global from here
 
-struct ActionArgs {
-  const float* ang;     // (n,3) angles (non-fused)
-  const float* mu;      // (n,3,3) or null (fused)
+// Launch arguments.  The tile kernel's start-up reads everything it needs ahead of its
+// first global load -- the fields of the first two 64-byte lines -- as one batch of scalar
+// loads behind one wait (fwd_tile_body): the scalar cache is cold at every launch, and each
+// separate fetch of a line is a serial round trip that every wave of every block pays before
+// its first v load is in flight.  64-byte aligned so that the lines below are lines of the
+// kernel-argument segment.
+struct alignas(64) ActionArgs {
+  // line 0
   const float* v;       // (n,3) algebra vector (fused)
   const float* F;       // spectrum
-  int64_t Fstride;      // 0 (shared) or M*C
   void* out;            // (n,M,C)
   float* ang_out;       // optional (fused)
   int64_t n;
-  int64_t MC;
-  int C, Sw, transpose;
-  int fpitch;           // tile kernel: floats per wave-private spectrum slice in LDS
-  int write_through;    // tile kernel: 1 = sc1 (write-through) stores, 0 = nt stores, 2 = plain (A/B)
+  int Sw;
   int prio;             // tile kernel wave priority: 2 = prologue at s_setprio 3, chain at 0
                         // (default); A/B: 0 off, 1 flush at 3, 3 = 2 + flush at 2
   int task_spread;      // tile kernel: prologue task t on lane t / nw of wave t % nw (1) instead
                         // of thread t (0: all tasks in wave 0)
-  int ang_order;        // tile kernel, mu-free fused: 0 = angles written before the spectrum
-                        // loads are issued (default), 1 = after them (A/B)
+  int transpose;
+  int ang_order;        // tile kernel, mu-free fused: where the angle waves run the maths of
+                        // ang_out: 0 = before they issue their spectrum loads (default),
+                        // 1 = after the prologue barrier, their v load in flight with their
+                        // spectrum loads (A/B)
+  int write_through;    // tile kernel: 1 = sc1 (write-through) stores, 0 = nt stores, 2 = plain (A/B)
+  // line 1
+  unsigned seg_mask[kMaxSeg];   // tile kernel: degree set of wave k (bit l = degree l)
+  // the rest: other kernels, and the tile kernel's run-time-C / mean-rotation instantiations
+  const float* ang;     // (n,3) angles (non-fused)
+  const float* mu;      // (n,3,3) or null (fused)
+  int64_t Fstride;      // 0 (shared) or M*C
+  int64_t MC;
+  int C;
+  int fpitch;           // tile kernel: floats per wave-private spectrum slice in LDS
   unsigned long long* stamps;  // phase timestamps (A/B timeline tool; null in the product)
   int seg_lo[kMaxSeg + 1];      // non-tile kernel / run-time-C tile: contiguous degree ranges
-  unsigned seg_mask[kMaxSeg];   // tile kernel: degree set of wave k (bit l = degree l)
 };
+static_assert(offsetof(ActionArgs, seg_mask) == 64 && offsetof(ActionArgs, ang) == 128,
+              "ActionArgs: the tile kernel's start-up fields fill the first two 64-byte lines");
 
-// Phase timestamps for tools/timeline.py (the A/B build's LV_STAMPS=1; the product passes
-// null): lane 0 of each wave writes the 100 MHz real-time counter at phase k, slot
-// [block][wave < 16][k < 8].
+// Phase timestamps for tools/timeline.py (the A/B build's LV_STAMPS=1): lane 0 of each wave
+// writes the 100 MHz real-time counter at phase k, slot [block][wave < 16][k < 8].  Compiled
+// into the A/B library's kernels only (-DLV_AB_KNOBS, its own instantiation objects): the
+// product's kernels carry no stamp sites -- one of them was the first thing the tile kernel
+// did, a scalar test of a field the product always passes as null.
+#ifdef LV_AB_KNOBS
+constexpr bool kStamps = true;
+#else
+constexpr bool kStamps = false;
+#endif
 constexpr int64_t kStampBlocks = 16384;
 __device__ __forceinline__ void phase_stamp(unsigned long long* st, int wave, int k) {
-  if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampBlocks)
-    st[((int64_t)blockIdx.x * 16 + wave) * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  if constexpr (kStamps) {
+    if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampBlocks)
+      st[((int64_t)blockIdx.x * 16 + wave) * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  }
 }
 // ... and at the end of each degree l of the chain, slot [block < 2048][wave][l < 24] after
 // the phase slots and the reduce kernel's 2 x 4096 (per-degree cost calibration).
 constexpr int64_t kStampDegBlocks = 2048;
 constexpr int64_t kStampDegBase = kStampBlocks * 16 * 8 + 2 * 4096;
 __device__ __forceinline__ void degree_stamp(unsigned long long* st, int wave, int l) {
-  if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampDegBlocks)
-    st[kStampDegBase + ((int64_t)blockIdx.x * 16 + wave) * 24 + l] = __builtin_amdgcn_s_memrealtime();
+  if constexpr (kStamps) {
+    if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampDegBlocks)
+      st[kStampDegBase + ((int64_t)blockIdx.x * 16 + wave) * 24 + l] = __builtin_amdgcn_s_memrealtime();
+  }
 }
 
 

@@ -270,33 +270,27 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   // rows, so the slot is free to be overwritten; the block saves M*C*4 bytes of LDS
   // (l = 10: 35.7 -> 30.9 KB, 4 -> 5 blocks per CU).
   constexpr bool FT = CT > 0 && std::is_same_v<OutT, float>;
-  const int C = CT > 0 ? CT : a.C;
-  const int Sw = a.Sw;  // 64 / C, or fewer (plan: LDS per block vs blocks per CU)
-  const int64_t MC = CT > 0 ? (int64_t)(LT + 1) * (LT + 1) * CT : a.MC;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar branches
-  const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
-  const int j = lane / C;
-  const int c = lane - j * C;
+  const int tid = (int)threadIdx.x;
+  // Start-up: every launch argument the prologue reads ahead of its first global load, as
+  // ONE batch of scalar loads behind one wait (the empty asm needs them all in registers
+  // here).  The scalar cache is cold at every launch; fetched where they were first used
+  // the fields took four serial round trips before the task lanes' v load was issued.
+  const float* const vin = FUSED ? a.v : a.ang;
+  const float* const aF = a.F;
+  void* const aout = a.out;
+  float* const aang = a.ang_out;
+  const int64_t an = a.n;
+  const int Sw = a.Sw;  // 64 / C, or fewer (plan: LDS per block vs blocks per CU)
+  const int prio = a.prio, spread = a.task_spread, transp = a.transpose;
+  const int ang_order = a.ang_order, wthrough = a.write_through;
   // this wave's degrees: a bit set (compile-time C: any set the planner balanced by cost);
   // run-time C keeps contiguous ranges [lo, hi) for its column-major spectrum slices
   const unsigned dmask = a.seg_mask[wave];
-  const int lo = a.seg_lo[wave], hi = a.seg_lo[wave + 1];
-  const int rows_lo = lo * lo;
-  const int frows = fseg_rows(lo, hi);
-  const int64_t s0 = grp * Sw;
-  const int Sv = (int)min((int64_t)Sw, a.n - s0);  // >= 1: grp < ceil(n / Sw)
-  const bool active = j < Sv;
-  const int stage_bytes = tile_stage_bytes(Sw, MC, (int)sizeof(OutT));
-  float* trig = lds + (stage_bytes >> 2);
-  OutT* gout = reinterpret_cast<OutT*>(a.out) + s0 * MC;
-  const int mis = (int)(reinterpret_cast<uintptr_t>(gout) & 15);
-  char* stage_b = reinterpret_cast<char*>(lds) + mis;  // LDS addr = global addr (mod 16)
-  // spectrum in LDS: CT > 0 the whole (M, C) row-major, staged by all threads of the block
-  // (FT: in the tile's last sample slot), else per-wave column-major slices of a.fpitch
-  float* const Fall = FT ? reinterpret_cast<float*>(stage_b) + (Sw - 1) * MC : trig + Sw * kRow;
-  float* Fw = Fall + (CT > 0 ? 0 : wave * a.fpitch);
-  // 1. prologue task (sample jt, slot q); the host guarantees 3*Sw <= blockDim.x
+  const int nthr = (int)blockDim.x;
+  asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(prio), "s"(spread),
+               "s"(transp), "s"(ang_order), "s"(wthrough), "s"(dmask), "s"(nthr));
   // Wave priority (a.prio, the plan's default 2): the prologue (v / mu loads, exp -> ZYZ,
   // multiples, spectrum staging) issues at s_setprio 3 and the chain at 0, so on a CU that
   // holds blocks in different phases a new block's loads start ahead of the other blocks'
@@ -304,111 +298,168 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   // 20.96 -> 18.27 us, 65,536 63.6 -> 61.1, 262,144 256 -> 252; 4,096, where every block
   // starts at once, unchanged).  1 / 3: A/B variants with the flush raised.
   phase_stamp(a.stamps, wave, 0);
-  if (a.prio >= 2) __builtin_amdgcn_s_setprio(3);
+  if (prio >= 2) __builtin_amdgcn_s_setprio(3);
+  const int nw = nthr >> 6;
+  const int64_t s0 = grp * Sw;
+  const int Sv = (int)min((int64_t)Sw, an - s0);  // >= 1: grp < ceil(n / Sw)
+  // v (angles) and ang_out of the group through buffer resources based at its first sample:
+  // per-lane 32-bit byte offsets, no 64-bit address arithmetic on the lanes (as tile_flush
+  // addresses out)
+  const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(vin) + s0 * 3, 0, Sv * 12, kRawBufferFlags);
+  auto load3 = [&](int js, float x[3]) {
+    // (three 4-byte loads, which the compiler merges into one buffer_load_dwordx3)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vrs, js * 12 + 4 * i, 0, 0));
+  };
+  // 1. prologue task (sample jt, slot q); the host guarantees 3*Sw <= blockDim.x
   // task_spread: task t on lane t / nw of wave t % nw, so the prologue's serial chains run on
   // every SIMD of the CU instead of all in wave 0
-  const int t_task = a.task_spread ? lane * (nthr >> 6) + wave : tid;
+  const int t_task = spread ? lane * nw + wave : tid;
   const bool task = t_task < 3 * Sw;
-  const int jt = t_task / 3, q = t_task - 3 * (t_task / 3);
+  const int jt = (t_task * 683) >> 11, q = t_task - 3 * jt;  // t / 3, exact below 2,045
   const int64_t st = s0 + min(jt, Sv - 1);  // idle slots mirror a valid sample
   LaneIn in;
-  if (task) lane_load<FUSED, MAYMU>(a, st, in);
-  // The mu-free fused kernel writes ang_out (the product operator's saved angles) from
-  // waves 1 and 2, lanes j < Sv, during the prologue -- waves that only stage spectrum rows
-  // there, on other SIMDs than the task lanes of wave 0 -- instead of on the q = 0 task
-  // lanes, where quat_to_eazyz_fwd's atan2 / acos held wave 0's multiples by ~0.5 us per
-  // launch.  Same quaternion (exp_quat), so the same angles bit for bit.  Wave 1 writes
-  // alpha and gamma, wave 2 beta = saved_beta of the forward's own (cos, sin) pair (a
-  // longer chain than the acos it replaces: all three on wave 1 cost 0.11 us per launch at
-  // config 2, split 0.06 us); a two-wave block writes all three from wave 1, a one-wave
-  // block after its chain.
-  constexpr bool kAngLate = FUSED && !MAYMU;
-  const int ang_wave = (nthr >> 6) > 1 ? 1 : 0;
-  const int beta_wave = (nthr >> 6) > 2 ? 2 : ang_wave;
-  const bool ang_on = kAngLate && a.ang_out != nullptr && lane < Sv;
-  const bool ang_lane = ang_on && wave == ang_wave;
-  const bool beta_lane = ang_on && wave == beta_wave;
-  auto write_ang = [&](bool dirs, bool beta) {
-    float vang[3];
+  if (task) {
+    load3(min(jt, Sv - 1), in.v);
+    if constexpr (FUSED && MAYMU) {
+      if (a.mu) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) vang[i] = a.v[(s0 + lane) * 3 + i];
+        for (int i = 0; i < 9; ++i) in.mu[i] = a.mu[st * 9 + i];
+      }
+    }
+  }
+  const int C = CT > 0 ? CT : a.C;
+  const int64_t MC = CT > 0 ? (int64_t)(LT + 1) * (LT + 1) * CT : a.MC;
+  const int j = lane / C;
+  const int c = lane - j * C;
+  const int lo = a.seg_lo[wave], hi = a.seg_lo[wave + 1];
+  const int rows_lo = lo * lo;
+  const int frows = fseg_rows(lo, hi);
+  const bool active = j < Sv;
+  const int stage_bytes = tile_stage_bytes(Sw, MC, (int)sizeof(OutT));
+  float* trig = lds + (stage_bytes >> 2);
+  OutT* gout = reinterpret_cast<OutT*>(aout) + s0 * MC;
+  const int mis = (int)(reinterpret_cast<uintptr_t>(gout) & 15);
+  char* stage_b = reinterpret_cast<char*>(lds) + mis;  // LDS addr = global addr (mod 16)
+  // spectrum in LDS: CT > 0 the whole (M, C) row-major, staged by all threads of the block
+  // (FT: in the tile's last sample slot), else per-wave column-major slices of a.fpitch
+  float* const Fall = FT ? reinterpret_cast<float*>(stage_b) + (Sw - 1) * MC : trig + Sw * kRow;
+  float* Fw = Fall + (CT > 0 ? 0 : wave * a.fpitch);
+  // The mu-free fused kernel writes ang_out (the product operator's saved angles) from
+  // waves 1 and 2, lanes j < Sv -- waves that only stage spectrum rows in the prologue, on
+  // other SIMDs than the task lanes of wave 0 -- instead of on the q = 0 task lanes, where
+  // quat_to_eazyz_fwd's atan2 / acos held wave 0's multiples by ~0.5 us per launch.  Same
+  // quaternion (exp_quat), so the same angles bit for bit.  Wave 1 writes alpha and gamma,
+  // wave 2 beta = saved_beta of the forward's own (cos, sin) pair (a longer chain than the
+  // acos it replaces: all three on wave 1 cost 0.11 us per launch at config 2, split
+  // 0.06 us); a two-wave block writes all three from wave 1, a one-wave block from wave 0.
+  // a.ang_order 0 (the product): they run that maths (~350 VALU: exp_quat, two generic
+  // atan2) before they issue their spectrum loads.  1 (A/B): their v load goes out with the
+  // spectrum loads and the maths runs AFTER the prologue barrier, ahead of their chain (the
+  // planner then charges them for it, balance_masks); that takes them off the path to the
+  // barrier but puts ~550 wave-instructions on the VALU-bound chain: 6.74-6.77 us against
+  // 6.65-6.68 at config 2 (profiles/r07_ab_startup_c2.txt), so 0 stays.  A one-wave block
+  // always writes behind the barrier.
+  constexpr bool kAngLate = FUSED && !MAYMU;
+  const int ang_wave = nw > 1 ? 1 : 0;
+  const int beta_wave = nw > 2 ? 2 : ang_wave;
+  const bool ang_on = kAngLate && aang != nullptr && lane < Sv;
+  const bool dirs_lane = ang_on && wave == ang_wave, beta_lane = ang_on && wave == beta_wave;
+  const bool ang_early = ang_order == 0 && nw > 1;
+  float vang[3] = {0.f, 0.f, 0.f};
+  if (dirs_lane || beta_lane) load3(lane, vang);
+  auto write_ang = [&]() {
+    const __amdgpu_buffer_rsrc_t ars =
+        __builtin_amdgcn_make_buffer_rsrc(aang + s0 * 3, 0, Sv * 12, kRawBufferFlags);
     const ExpQuat e = exp_quat(vang);
-    if (dirs) {
+    if (dirs_lane) {
       float ang[3];
       quat_to_eazyz_fwd(e.qr, ang);
-      a.ang_out[(s0 + lane) * 3 + 0] = ang[0];
-      a.ang_out[(s0 + lane) * 3 + 2] = ang[2];
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, ang[0]), ars, lane * 12, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, ang[2]), ars, lane * 12 + 8, 0, 0);
     }
-    if (beta) {
+    if (beta_lane) {
       float cb, sb;
       exp_beta(e, cb, sb);
-      a.ang_out[(s0 + lane) * 3 + 1] = saved_beta(cb, sb);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, saved_beta(cb, sb)), ars,
+                                            lane * 12 + 4, 0, 0);
     }
   };
-  const bool early_dirs = ang_lane && ang_wave == 1, early_beta = beta_lane && beta_wave >= 1;
-  // a.ang_order 0 (default): wave 1 writes the angles before it issues its spectrum loads,
-  // so its two global round trips run back to back and it reaches the prologue barrier last
-  // (timeline at 4,096: loads landed 1.08 us after wave start vs 0.52-0.68 on the other
-  // waves, barrier at 1.73 with the multiples done at 1.28); 1 (A/B): after them, so the v
-  // load and the spectrum loads are in flight together.  A/B at config 2: 7.15 / 7.16 us
-  // for 1 against 7.14 / 7.13 for 0 (profiles/r06_ab_ang_order_c2.txt) -- the other waves'
-  // chains hide the late wave, so the round-5 order stays
-  if ((early_dirs || early_beta) && a.ang_order == 0) write_ang(early_dirs, early_beta);
+  if constexpr (kAngLate) {
+    if ((dirs_lane || beta_lane) && ang_early) write_ang();
+  }
   // 2. spectrum staging: every load issued now (before the prologue maths), the LDS writes
-  //    after it.  CT > 0: element e = tid + k * nthr of the whole (M, C) spectrum, at most
-  //    kFPer per thread for the smallest block the plan makes (2 waves), a batched loop
-  //    beyond; else this wave's column-major slice.
+  //    after it.  CT > 0: element e = tid + k * nthr of the whole (M, C) spectrum, in as
+  //    many slots as the block's thread count needs (three tiers: from 7, from 4, fewer
+  //    waves; a batched loop beyond kFPerCap slots).  A lane past the end re-stages the
+  //    last element (clamped index: the same value to the same LDS word), so no slot is
+  //    guarded -- sized for the 2-wave block and guarded twice, the 10 slots at l = 10
+  //    cost the 7-wave block 20 exec-mask regions of which 3 + 3 did work.
+  //    Run-time C: this wave's column-major slice.
   constexpr int kFPer = FG ? 1 : (CT > 0 ? ((LT + 1) * (LT + 1) * (CT > 0 ? CT : 1) + 127) / 128 : 6);
   constexpr int kFPerCap = kFPer < 18 ? kFPer : 18;
+  constexpr int kMCT = (LT + 1) * (LT + 1) * (CT > 0 ? CT : 1);
+  constexpr int kSlots7 = (kMCT + 447) / 448 < kFPerCap ? (kMCT + 447) / 448 : kFPerCap;
+  constexpr int kSlots4 = (kMCT + 255) / 256 < kFPerCap ? (kMCT + 255) / 256 : kFPerCap;
+  static_assert(CT == 0 || kSlots4 * 256 >= kMCT, "tile staging: the 4-wave tier covers the spectrum");
   float fv[kFPerCap];
   const int fcnt = FG ? 0 : (CT > 0 ? (int)MC : (hi * hi - rows_lo) * C);
   const int fstr = CT > 0 ? nthr : 64;
   const int fbase = CT > 0 ? tid : lane;
-  const float* fsrc = a.F + (CT > 0 ? 0 : rows_lo * C);
+  const float* fsrc = aF + (CT > 0 ? 0 : rows_lo * C);
+  if constexpr (CT > 0) {
+    auto ld = [&](auto K) { fv[LV_CV(K)] = fsrc[min(tid + nthr * LV_CV(K), kMCT - 1)]; };
+    if (nw >= 7) sfor<kSlots7>(ld);
+    else if (nw >= 4) sfor<kSlots4>(ld);
+    else sfor<kFPerCap>(ld);
+  } else {
 #pragma unroll
-  for (int k = 0; k < kFPerCap; ++k) {
-    const int e = fbase + fstr * k;
-    fv[k] = e < fcnt ? fsrc[e] : 0.f;
+    for (int k = 0; k < kFPerCap; ++k) {
+      const int e = fbase + fstr * k;
+      fv[k] = e < fcnt ? fsrc[e] : 0.f;
+    }
   }
-  if ((early_dirs || early_beta) && a.ang_order != 0) write_ang(early_dirs, early_beta);
-  if (a.stamps) {  // A/B timeline: when this wave's loads (v; spectrum) have landed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    phase_stamp(a.stamps, wave, 5);
+  if constexpr (kStamps) {
+    if (a.stamps) {  // A/B timeline: when this wave's loads (v; spectrum) have landed
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      phase_stamp(a.stamps, wave, 5);
+    }
   }
   if (task) {
     float cq, sq;
     if constexpr (FUSED && !MAYMU) {
       // z = exp(v): this thread's slot only (transpose: slot q takes angle 2 - q, sine negated)
-      // ang_out is not written here: wave 1 writes it during the prologue (above; a one-wave
-      // block after its chain), since its atan2 / acos kept the multiples waiting on the
-      // q = 0 lanes
+      // ang_out is not written here (see above)
       float qr[4];
-      exp_to_zyz_slot(in.v, a.transpose ? 2 - q : q, cq, sq, qr);
-      if (a.transpose) sq = -sq;
+      exp_to_zyz_slot(in.v, transp ? 2 - q : q, cq, sq, qr);
+      if (transp) sq = -sq;
     } else {
       float c1[3], s1[3];
-      lane_angles<FUSED, MAYMU>(a, in, st, jt < Sv, q, FUSED && a.ang_out != nullptr, c1, s1);
+      lane_angles<FUSED, MAYMU>(a, in, st, jt < Sv, q, FUSED && aang != nullptr, c1, s1);
       cq = q == 0 ? c1[0] : (q == 1 ? c1[1] : c1[2]);
       sq = q == 0 ? s1[0] : (q == 1 ? s1[1] : s1[2]);
     }
-    if (a.stamps) phase_stamp(a.stamps, wave, 6);
+    phase_stamp(a.stamps, wave, 6);
     trig_row_fill1<LT>(trig + jt * kRow, cq, sq, q, LT);
-    if (a.stamps) phase_stamp(a.stamps, wave, 7);
+    phase_stamp(a.stamps, wave, 7);
   }
   if constexpr (FG) {
   } else if constexpr (CT > 0) {
+    auto wr = [&](auto K) { Fw[min(tid + nthr * LV_CV(K), kMCT - 1)] = fv[LV_CV(K)]; };
+    if (nw >= 7) sfor<kSlots7>(wr);
+    else if (nw >= 4) sfor<kSlots4>(wr);
+    else {
+      sfor<kFPerCap>(wr);
+      for (int e0 = fbase + fstr * kFPerCap; e0 < fcnt; e0 += 8 * fstr) {
+        float t8[8];
 #pragma unroll
-    for (int k = 0; k < kFPerCap; ++k) {
-      const int e = fbase + fstr * k;
-      if (e < fcnt) Fw[e] = fv[k];
-    }
-    for (int e0 = fbase + fstr * kFPerCap; e0 < fcnt; e0 += 8 * fstr) {
-      float t8[8];
+        for (int u = 0; u < 8; ++u) t8[u] = e0 + fstr * u < fcnt ? fsrc[e0 + fstr * u] : 0.f;
 #pragma unroll
-      for (int u = 0; u < 8; ++u) t8[u] = e0 + fstr * u < fcnt ? fsrc[e0 + fstr * u] : 0.f;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (e0 + fstr * u < fcnt) Fw[e0 + fstr * u] = t8[u];
+        for (int u = 0; u < 8; ++u)
+          if (e0 + fstr * u < fcnt) Fw[e0 + fstr * u] = t8[u];
+      }
     }
   } else {
 #pragma unroll
@@ -427,11 +478,14 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   block_sync_lds();
   phase_stamp(a.stamps, wave, 1);
 
-  if (a.prio >= 2) __builtin_amdgcn_s_setprio(0);
+  if (prio >= 2) __builtin_amdgcn_s_setprio(0);
+  if constexpr (kAngLate) {
+    if ((dirs_lane || beta_lane) && !ang_early) write_ang();
+  }
   OutT* st_lane = reinterpret_cast<OutT*>(stage_b) + j * MC + c;
   const float* tj = trig + min(j, Sw - 1) * kRow;
   // spectrum column: LDS slice, or global (FG)
-  const float* Fl = FG ? a.F + c : (CT > 0 ? Fall + c : Fw + c * frows - rows_lo);
+  const float* Fl = FG ? aF + c : (CT > 0 ? Fall + c : Fw + c * frows - rows_lo);
   const int fstep = (FG || CT > 0) ? C : 1;  // stride between consecutive rows of a column
 
   sfor<LT + 1>([&](auto Lc) {
@@ -453,16 +507,15 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
           d += C;
         });
       }
-      if (a.stamps) degree_stamp(a.stamps, wave, l);
+      degree_stamp(a.stamps, wave, l);
     }
   });
-  if (ang_lane && ang_wave == 0) write_ang(true, true);
   phase_stamp(a.stamps, wave, 2);
   block_sync_lds();
   phase_stamp(a.stamps, wave, 3);
-  if (a.prio == 1) __builtin_amdgcn_s_setprio(3);  // A/B: the flush ahead of other waves' chains
-  else if (a.prio == 3) __builtin_amdgcn_s_setprio(2);
-  tile_flush_rt<OutT>(gout, stage_b, mis, Sv * (int)MC * (int)sizeof(OutT), a.write_through);
+  if (prio == 1) __builtin_amdgcn_s_setprio(3);  // A/B: the flush ahead of other waves' chains
+  else if (prio == 3) __builtin_amdgcn_s_setprio(2);
+  tile_flush_rt<OutT>(gout, stage_b, mis, Sv * (int)MC * (int)sizeof(OutT), wthrough);
   phase_stamp(a.stamps, wave, 4);
 }
 
