@@ -73,6 +73,10 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="capture the whole step (fwd, bwd, all-reduce, clip, Adam) in a "
                          "hipGraph and time its replays")
+    ap.add_argument("--equivariance", type=float, default=None, metavar="LAMB",
+                    help="add the SO(2)-equivariance regulariser (lie_vae.losses) with this "
+                         "weight: a second encoder pass on the rotated batch, the rotate "
+                         "kernel and the loss kernel per step")
     ap.add_argument("--iwae", type=int, default=0, metavar="K",
                     help="time the IWAE log-likelihood (n=500) over K images instead")
     ap.add_argument("--iwae-n", type=int, default=500)
@@ -120,9 +124,11 @@ def main():
     if args.iwae:
         return bench_iwae(args, model, env, dev)
     rec = time_train_steps(model, dev, world, rank, args.global_batch, args.steps, args.warmup,
-                           amp=args.amp, graph=args.graph, fused_adam=args.adam == "fused")
+                           amp=args.amp, graph=args.graph, fused_adam=args.adam == "fused",
+                           equivariance_lamb=args.equivariance)
     if rank == 0:
-        rec["config"].update({"l_max": args.lmax, "deconv_hidden": args.deconv_hidden,
+        rec["config"].update({"equivariance_lamb": args.equivariance,
+                              "l_max": args.lmax, "deconv_hidden": args.deconv_hidden,
                               "mean_mode": args.mean_mode, "channels_last": args.channels_last,
                               "miopen_find": args.find, "conv_gemm": args.conv_gemm,
                               "deconv": args.deconv, "fused_relu": args.fused_relu,
@@ -141,19 +147,20 @@ def _backend_name():
 
 
 def time_train_steps(model, dev, world, rank, global_batch, steps, warmup, amp="off",
-                     graph=False, fused_adam=True, flops=True, rounds=1):
+                     graph=False, fused_adam=True, flops=True, rounds=1, equivariance_lamb=None):
     """Time `steps` DPTrainer steps (elbo fwd + bwd + bucketed all-reduce at world > 1 +
     global clip + Adam) on a synthetic per-rank shard after `warmup` steps; barrier +
     synchronize on both sides, max over ranks.  With rounds > 1 the timed loop runs that
     many times back to back and the record's time is the median round (every round's time
     is in the record): one stall of a few tens of ms inside a 40-ms window (seen once on a
     driver box: a 10.6 ms bf16 step against 3.9-4.3 ms in every rerun) no longer sets the
-    figure.  Returns the record (rank 0 prints it)."""
+    figure.  equivariance_lamb adds the equivariance regulariser to the step.  Returns the
+    record (rank 0 prints it)."""
     import torch.distributed as dist
     from lie_vae.experiments.train_dp import DPTrainer, param_count
     trainer = DPTrainer(model, lr=1e-3, clip_grads=1e-5,
                         amp_dtype=torch.bfloat16 if amp == "bf16" else None,
-                        graph=graph, fused_adam=fused_adam)
+                        graph=graph, fused_adam=fused_adam, equivariance_lamb=equivariance_lamb)
     B = global_batch // world
     g = torch.Generator(device="cpu").manual_seed(100 + rank)
     x = torch.rand(B, 3, 64, 64, generator=g).to(dev)

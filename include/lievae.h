@@ -301,6 +301,42 @@ int lv_deconv4s2_pack_weight_f32(const float* w, float* wt, int Cin, int Cout, v
 int lv_deconv4s2_fwd_f32(const float* x, const float* wt, const float* bias, float* y, float* y_cl,
                          int64_t N, int H, int W, int Cin, int Cout, int flags, void* stream);
 
+/* ---- encoder regularisers (csrc/image.hip) ---------------------------------------------
+ * EquivarianceLoss.rotate: losses/equivariance_loss.py:50-57 (affine_grid + grid_sample in
+ * one pass).  img, out (N, C, H, W) fp32; cs (N, 2) = (cos, sin) of each image's angle, the
+ * convention of the s2s1 map above.  out[n, c] = img[n, c] sampled bilinearly, zeros outside,
+ * at the positions the affine matrix [[c, -s, 0], [s, c, 0]] gives in normalised
+ * coordinates, under either align_corners convention (0: torch's present default, what the
+ * reference runs with today; 1: the default when it was written; equal to rounding for
+ * H == W).  Positions are evaluated in pixel space about the image centre, so (c, s) =
+ * (1, 0) copies the input bit for bit, (-1, 0) is the exact half turn, and (0, +-1) are the
+ * exact quarter turns when H == W.  A plane of at most 64 KB is staged in LDS by one block
+ * per (n, c); larger planes, or flags & LV_ROTATE_DIRECT, read their taps from global
+ * memory.  Both paths give the same bits.  No backward: the reference never differentiates
+ * the image, and the angles carry no gradient.  N * C <= INT_MAX. */
+#define LV_ROTATE_DIRECT 1
+int lv_rotate_bilinear_fwd(const float* img, const float* cs, float* out, int64_t N, int C, int H,
+                           int W, int align_corners, int flags, void* stream);
+/* Host-only dispatch of the call above: plan[0] staged path (1) or direct (0), [1] grid
+ * blocks, [2] threads per block, [3] dynamic LDS bytes per block. */
+#define LV_ROTATE_PLAN_LEN 4
+int lv_rotate_plan(int64_t N, int C, int H, int W, int flags, int64_t* plan);
+/* EquivarianceLoss.forward: losses/equivariance_loss.py:28-36 with lie_tools.py:67-78.
+ * diffs[n] = sum_ij (g_n enc_n - enc_rot_n)_ij^2, g_n the rotation about the x axis by the
+ * angle of cs[n] = (cos, sin); cs (n, 2), enc and enc_rot (n, 3, 3), diffs (n).  The backward
+ * takes gdiffs (n) and writes g_enc and g_enc_rot (n, 3, 3). */
+int lv_equivariance_diff_fwd(const float* cs, const float* enc, const float* enc_rot, float* diffs,
+                             int64_t n, void* stream);
+int lv_equivariance_diff_bwd(const float* cs, const float* enc, const float* enc_rot,
+                             const float* gdiffs, float* g_enc, float* g_enc_rot, int64_t n,
+                             void* stream);
+/* EncoderContinuityLoss.forward: losses/encoder_continuity_loss.py:18-20.  enc (rows, D),
+ * rows even; rows 2i and 2i+1 are a pair: diffs[i] = sum_k (enc[2i, k] - enc[2i+1, k])^2,
+ * diffs (rows / 2).  The backward takes gdiffs (rows / 2) and writes g_enc (rows, D). */
+int lv_pair_sqdist_fwd(const float* enc, float* diffs, int64_t rows, int D, void* stream);
+int lv_pair_sqdist_bwd(const float* enc, const float* gdiffs, float* g_enc, int64_t rows, int D,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,14 @@ _SIGS["lv_channel_sum_bf16"] = [_P, _P, _P, _I64, _I, _P]
 _SIGS["lv_accumulate_bf16_f32"] = [_P, _P, _I64, _P]
 _SIGS["lv_bn_lrelu_fwd_bf16"] = [_P, _P, _P, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P, _I64, _I, _P]
 _SIGS["lv_bn_lrelu_bwd_bf16"] = [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I64, _I, _P]
+# encoder regularisers (csrc/image.hip)
+_SIGS["lv_rotate_bilinear_fwd"] = [_P, _P, _P, _I64, _I, _I, _I, _I, _I, _P]
+_SIGS["lv_rotate_plan"] = [_I64, _I, _I, _I, _I, _P]
+_SIGS["lv_equivariance_diff_fwd"] = [_P, _P, _P, _P, _I64, _P]
+_SIGS["lv_equivariance_diff_bwd"] = [_P, _P, _P, _P, _P, _P, _I64, _P]
+_SIGS["lv_pair_sqdist_fwd"] = [_P, _P, _I64, _I, _P]
+_SIGS["lv_pair_sqdist_bwd"] = [_P, _P, _P, _I64, _I, _P]
+LV_ROTATE_DIRECT = 1  # include/lievae.h
 _RESTYPES = {"lv_group_action_bwd_workspace": _SZ, "lv_last_error": ctypes.c_char_p,
              "lv_deconv4s2_packed_weight_elems": _SZ, "lv_deconv4s2_small_packed_weight_elems": _SZ,
              "lv_deconv4s2_packed_weight_elems_f32": _SZ,
@@ -160,7 +168,15 @@ def plan(kind, *args):
     return d
 
 
-TORCH_OPS_PATH = os.environ.get("LIEVAE_TORCH_OPS_LIB", os.path.join(_HERE, "liblievae_torch.so"))
+def rotate_plan(N, C, H, W, flags=0):
+    """Host-only dispatch of lv_rotate_bilinear_fwd as a dict; no GPU call
+    (include/lievae.h LV_ROTATE_PLAN_LEN)."""
+    buf = (ctypes.c_int64 * 4)()
+    call("lv_rotate_plan", N, C, H, W, flags, buf)
+    return dict(zip(("staged", "blocks", "threads", "lds_bytes"), buf))
+
+
+TORCH_OPS_PATH =os.environ.get("LIEVAE_TORCH_OPS_LIB", os.path.join(_HERE, "liblievae_torch.so"))
 _torch_ops = None
 
 

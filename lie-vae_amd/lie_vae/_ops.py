@@ -377,6 +377,88 @@ def wigner_blocks(angles, L):
     return D
 
 
+# ------------------------------------------------------ encoder regularisers
+def rotate_images(img, cs, align_corners=False, flags=0):
+    """EquivarianceLoss.rotate on the HIP path (losses/equivariance_loss.py:50-57): img
+    (N, C, H, W) rotated per image by the angle of cs (N, 2) = (cos, sin), bilinear taps,
+    zeros outside.  No backward (the reference never differentiates the image): an input
+    that requires grad is refused.  flags: _lib.LV_ROTATE_DIRECT forces the direct path."""
+    assert img.dim() == 4, f"img must be (N,C,H,W), got {tuple(img.shape)}"
+    assert tuple(cs.shape) == (img.shape[0], 2), \
+        f"cs must be ({img.shape[0]},2), got {tuple(cs.shape)}"
+    if img.requires_grad or cs.requires_grad:
+        raise RuntimeError("rotate_images has no backward (the reference rotates its input "
+                           "image with angles drawn without gradient); detach the inputs")
+    _lib.require_device(img, cs)
+    img, cs = _f32c(img), _f32c(cs)
+    N, C, H, W = img.shape
+    out = torch.empty_like(img)
+    call("lv_rotate_bilinear_fwd", ptr(img), ptr(cs), ptr(out), N, C, H, W,
+         int(bool(align_corners)), flags, _lib.stream_of(img.device))
+    return out
+
+
+class _EquivarianceDiff(torch.autograd.Function):
+    """diffs[n] = sum (g_n enc_n - enc_rot_n)^2, g = s2s1rodrigues(e_x, cs) --
+    losses/equivariance_loss.py:28-36.  cs carries no gradient (theta is drawn)."""
+
+    @staticmethod
+    def forward(ctx, cs, enc, enc_rot):
+        cs, enc, enc_rot = _prep(cs), _prep(enc), _prep(enc_rot)
+        n = cs.shape[0]
+        diffs = _empty((n,), enc)
+        call("lv_equivariance_diff_fwd", ptr(cs), ptr(enc), ptr(enc_rot), ptr(diffs), n,
+             _lib.stream_of(enc.device))
+        ctx.save_for_backward(cs, enc, enc_rot)
+        return diffs
+
+    @staticmethod
+    def backward(ctx, g):
+        cs, enc, enc_rot = ctx.saved_tensors
+        ge, gr = torch.empty_like(enc), torch.empty_like(enc_rot)
+        call("lv_equivariance_diff_bwd", ptr(cs), ptr(enc), ptr(enc_rot), ptr(_prep(g)), ptr(ge),
+             ptr(gr), cs.shape[0], _lib.stream_of(enc.device))
+        return None, ge, gr
+
+
+def equivariance_diff(cs, enc, enc_rot):
+    """cs (n, 2), enc and enc_rot (n, 3, 3) -> diffs (n); differentiable in both encodings."""
+    n = cs.shape[0]
+    assert tuple(cs.shape) == (n, 2), f"cs must be (n,2), got {tuple(cs.shape)}"
+    assert tuple(enc.shape) == (n, 3, 3) and tuple(enc_rot.shape) == (n, 3, 3), \
+        f"enc and enc_rot must be ({n},3,3), got {tuple(enc.shape)} and {tuple(enc_rot.shape)}"
+    _lib.require_device(cs, enc, enc_rot)
+    return _EquivarianceDiff.apply(cs.detach(), enc, enc_rot)
+
+
+class _PairSqdist(torch.autograd.Function):
+    """diffs[i] = sum (enc[2i] - enc[2i+1])^2 -- losses/encoder_continuity_loss.py:18-20."""
+
+    @staticmethod
+    def forward(ctx, enc):
+        enc = _prep(enc)
+        rows, D = enc.shape
+        diffs = _empty((rows // 2,), enc)
+        call("lv_pair_sqdist_fwd", ptr(enc), ptr(diffs), rows, D, _lib.stream_of(enc.device))
+        ctx.save_for_backward(enc)
+        return diffs
+
+    @staticmethod
+    def backward(ctx, g):
+        (enc,) = ctx.saved_tensors
+        ge = torch.empty_like(enc)
+        call("lv_pair_sqdist_bwd", ptr(enc), ptr(_prep(g)), ptr(ge), enc.shape[0], enc.shape[1],
+             _lib.stream_of(enc.device))
+        return ge
+
+
+def pair_sqdist(enc):
+    """enc (2n, D) -> diffs (n): squared distance of adjacent rows."""
+    assert enc.dim() == 2, f"enc must be (rows, D), got {tuple(enc.shape)}"
+    _lib.require_device(enc)
+    return _PairSqdist.apply(enc)
+
+
 s2s1 = _S2S1.apply
 s2s2 = _S2S2.apply
 so3_sample = _SO3Sample.apply

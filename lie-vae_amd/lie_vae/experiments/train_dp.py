@@ -162,12 +162,18 @@ class DPTrainer:
     the DP step equals the single-device step on the concatenated batch, as the
     reference's one-device training computes it.  Off by default: per-rank statistics
     need no forward collective.
+
+    ``equivariance_lamb`` / ``encoder_continuity_lamb`` (a number or a schedule of the global
+    step, None = off) add the encoder regularisers of ``lie_vae.losses`` after the ELBO, as
+    unsupervised.py:100-106 does, on the latest sample ``model.z[0][0]``; the equivariance
+    term runs a second encoder pass on the rotated batch.
     """
 
     def __init__(self, model, lr=1e-3, weight_decay=0.0, clip_grads=1e-5, beta=1.0,
                  elbo_samples=1, bucket_bytes=32 << 20, group=None, broadcast=True,
                  control=None, control_p=1, selective_clip=False, nan_check=False,
-                 amp_dtype=None, graph=False, sync_bn=False, fused_adam=None):
+                 amp_dtype=None, graph=False, sync_bn=False, fused_adam=None,
+                 equivariance_lamb=None, encoder_continuity_lamb=None):
         if sync_bn and dist.is_initialized() and dist.get_world_size(group) > 1:
             from .nets import to_sync_batchnorm
             model = to_sync_batchnorm(model, process_group=group)
@@ -182,6 +188,16 @@ class DPTrainer:
         self.selective_clip = selective_clip
         self.nan_check = nan_check
         self.it = 0
+        # the encoder regularisers of unsupervised.py:44-56 (no log: the trainer keeps no
+        # host-side reporting inside the step)
+        self.equivariance_loss = self.encoder_continuity_loss = None
+        if equivariance_lamb is not None:
+            from ..losses import EquivarianceLoss
+            self.equivariance_loss = EquivarianceLoss(model, lamb=equivariance_lamb)
+        if encoder_continuity_lamb is not None:
+            from ..losses import EncoderContinuityLoss
+            self.encoder_continuity_loss = EncoderContinuityLoss(
+                model, lamb=encoder_continuity_lamb)
         if dist.is_initialized() and broadcast:
             for t in list(model.parameters()) + list(model.buffers()):
                 dist.broadcast(t.data, src=0, group=group)
@@ -225,6 +241,11 @@ class DPTrainer:
             loss = (recon + self.control * torch.abs(beta - kl)).mean()
         else:
             loss = (recon + self.control * (beta - kl) ** 2).mean()
+        # unsupervised.py:100-106, with the model's latest sample; `it` is the global step
+        if self.equivariance_loss is not None:
+            loss = loss + self.equivariance_loss(x, self.model.z[0][0], self.it)
+        if self.encoder_continuity_loss is not None:
+            loss = loss + self.encoder_continuity_loss(self.model.z[0][0], self.it)
         return loss, recon, kl
 
     def clip_params(self):
@@ -297,6 +318,12 @@ class DPTrainer:
             raise ValueError("capture() needs a constant, non-zero beta")
         if self.nan_check:
             raise ValueError("capture() cannot run the per-step NaN check")
+        for name, term in (("equivariance_lamb", self.equivariance_loss),
+                           ("encoder_continuity_lamb", self.encoder_continuity_loss)):
+            if term is not None and callable(term.lamb) and \
+                    not isinstance(term.lamb, ConstantSchedule):
+                raise ValueError(f"capture() needs a constant {name} (a number or a "
+                                 "ConstantSchedule): the graph bakes its value in")
         if self.ar.world > 1 and dist.get_backend(self.ar.group) != "nccl":
             raise ValueError("capture() with world > 1 needs the nccl (RCCL) backend: a "
                              f"{dist.get_backend(self.ar.group)} all-reduce cannot be captured "
