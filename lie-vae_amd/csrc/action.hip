@@ -403,7 +403,8 @@ constexpr double kTileSegCostFew = 300.0;    // -> 7 waves at l = 10
 constexpr double kTileSegCostMid = 260.0;    // -> 8
 constexpr double kTileSegCostLarge = 560.0;  // -> 4
 constexpr int64_t kTileFewGroupsPerCU = 4, kTileMidGroupsPerCU = 16;
-constexpr double kTilePrologue = 60.0;       // per-wave fixed cost: spectrum slice, multiples reads
+constexpr int kTileClasses = 0;              // block priority classes at <= kTileFewGroupsPerCU: off (plan_tile)
+constexpr double kTilePrologue = 60.0;      // per-wave fixed cost: spectrum slice, multiples reads
 // round 6 (7 / 8 waves per block): write-through still wins at 6,144 samples (29.7 MB:
 // 8.7-8.8 vs 9.0-9.1 us) and loses from 8,192 (39.6 MB: 11.7 vs 11.4; profiles/r06_ab_wt.txt)
 constexpr int64_t kWriteThroughMaxBytes = 32ll << 20;
@@ -464,7 +465,7 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   static const int kEnvTile = LV_KNOB("LV_TILE", 1);
   static const int kEnvWT = LV_KNOB("LV_TILE_WT", -1);
   static const int kEnvTileNseg = LV_KNOB("LV_TILE_NSEG", 0);  // A/B testing only
-  static const int kEnvPrio = LV_KNOB("LV_TILE_PRIO", 2);      // wave priority phases (ActionArgs)
+  static const int kEnvPrio = LV_KNOB("LV_TILE_PRIO", kTilePrio);     // wave priority phases (ActionArgs)
   // samples per block with compile-time C (A/B knob LV_TILE_SW)
   static const int kEnvSw = LV_KNOB("LV_TILE_SW", 0);
   if (!kEnvTile) return false;
@@ -520,7 +521,27 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   a.prio = kEnvPrio;
   static const int kEnvSpread = LV_KNOB("LV_TILE_SPREAD", 0);  // A/B: prologue tasks over all waves
   a.task_spread = kEnvSpread;
-  a.ang_order = kEnvAngOrder;
+  a.ang_order = (short)kEnvAngOrder;
+  // Block priority classes (ActionArgs::nclass, fwd_tile_body), A/B only: LV_TILE_NCLASS = 2
+  // or 3 classes where every block of the grid is resident at once -- up to
+  // kTileFewGroupsPerCU groups per CU, the 7-wave plan -- and none beyond, where blocks turn
+  // over and the prologue / chain priority phases interleave them.  LV_TILE_CLASS_MAP: a shift
+  // s (class = (blockIdx.x >> s) % classes; default log2(CUs), the block's turn on its CU, as
+  // blocks are dealt round-robin over the CUs; 3: the dealing round over the 8 XCDs) or 64
+  // (the workgroup's slot on its CU); LV_TILE_CLASS_FLUSH=1: the flush one priority up.  No
+  // mapping gained at config 2 (profiles/r08_ab_block_classes_c2.txt: 6.71-6.74 us against
+  // 6.70-6.76 without, 7.04-7.05 for the dealing round, 6.81-6.86 with the flush raised), so
+  // kTileClasses is 0 and the product's kernels do not hold the code.
+  static const int kEnvNclass = LV_KNOB("LV_TILE_NCLASS", kTileClasses);
+  static const int kEnvClassMap = LV_KNOB("LV_TILE_CLASS_MAP", -1);
+  static const int kEnvClassFlush = LV_KNOB("LV_TILE_CLASS_FLUSH", 0);
+  int cu_shift = 0;
+  while ((2 << cu_shift) <= cus) ++cu_shift;  // floor(log2(cus))
+  const int nclass = groups <= kTileFewGroupsPerCU * cus ? std::min(kEnvNclass, kMaxClasses) : 0;
+  a.nclass = (short)(nclass >= 2 ? nclass : 0);
+  int cmap = kEnvClassMap >= 0 ? (kEnvClassMap & (kClassMapSlot | kClassMapShift)) : cu_shift;
+  if (kEnvClassFlush) cmap |= kClassFlushUp;
+  a.class_map = (short)(a.nclass ? cmap : 0);
   p.tile = true;
   p.lds = lds;
   p.gx = (int)groups;
@@ -1099,6 +1120,27 @@ int lv_wigner_d_fwd(const float* ang, float* D, int64_t n, int L, void* stream) 
 }
 
 #ifdef LV_AB_KNOBS
+// Block priority classes of the forward's plan (A/B build, host only): info[0] tile kernel
+// (1) or grid-stride (0, never classed), [1] classes (0 = off), [2] ActionArgs::class_map,
+// [3..5] byte offsets of the two class fields and of the degree sets in ActionArgs (the tile
+// kernel's start-up reads the first two 64-byte lines in one batch of scalar loads).  cus > 0
+// plans for that many compute units, else for the device's.
+int lv_ab_fwd_classes(int fused, int64_t F_batch_stride, int out_dtype, int64_t n, int L, int C,
+                      int cus, int* info) {
+  clear_error();
+  LV_CHECK_ARG(info, "null info");
+  LV_CHECK_ARG(n > 0, "n must be > 0 (got %lld)", (long long)n);
+  FwdLaunch p;
+  if (int e = plan_fwd(fused != 0, F_batch_stride, out_dtype, n, L, C, cus > 0 ? cus : device_cus(), p)) return e;
+  info[0] = p.tile ? 1 : 0;
+  info[1] = p.a.nclass;
+  info[2] = p.a.class_map;
+  info[3] = (int)offsetof(ActionArgs, nclass);
+  info[4] = (int)offsetof(ActionArgs, class_map);
+  info[5] = (int)offsetof(ActionArgs, seg_mask);
+  return LV_OK;
+}
+
 // Timeline tool (A/B build): copy the phase-timestamp buffer to the host after a device
 // synchronise; returns the bytes copied (0 without LV_STAMPS=1).
 size_t lv_ab_stamps_copy(void* host, size_t bytes) {

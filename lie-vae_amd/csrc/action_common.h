@@ -30,13 +30,22 @@ struct alignas(64) ActionArgs {
   int Sw;
   int prio;             // tile kernel wave priority: 2 = prologue at s_setprio 3, chain at 0
                         // (default); A/B: 0 off, 1 flush at 3, 3 = 2 + flush at 2
-  int task_spread;      // tile kernel: prologue task t on lane t / nw of wave t % nw (1) instead
+  short task_spread;    // tile kernel: prologue task t on lane t / nw of wave t % nw (1) instead
                         // of thread t (0: all tasks in wave 0)
+  short nclass;         // tile kernel, A/B: block priority classes of the chain (0 = off, 2, 3):
+                        // a block of class k runs its chain (and flush) at s_setprio
+                        // nclass - 1 - k, so co-resident blocks end their chains apart and
+                        // their flushes leave one after the other (fwd_tile_body)
   int transpose;
-  int ang_order;        // tile kernel, mu-free fused: where the angle waves run the maths of
+  short ang_order;      // tile kernel, mu-free fused: where the angle waves run the maths of
                         // ang_out: 0 = before they issue their spectrum loads (default),
                         // 1 = after the prologue barrier, their v load in flight with their
                         // spectrum loads (A/B)
+  short class_map;      // how a block gets its class (tile_block_class): s >= 0: (blockIdx.x
+                        // >> s) % nclass -- 3: the 8 blocks dealt to the XCDs in one round
+                        // share a class, log2(8 * CUs per XCD): one class per block a CU holds;
+                        // kClassMapSlot: the workgroup's slot on its CU.  Bit 8 (kClassFlushUp,
+                        // A/B): the flush one priority above the chain's
   int write_through;    // tile kernel: 1 = sc1 (write-through) stores, 0 = nt stores, 2 = plain (A/B)
   // line 1
   unsigned seg_mask[kMaxSeg];   // tile kernel: degree set of wave k (bit l = degree l)
@@ -52,22 +61,51 @@ struct alignas(64) ActionArgs {
 };
 static_assert(offsetof(ActionArgs, seg_mask) == 64 && offsetof(ActionArgs, ang) == 128,
               "ActionArgs: the tile kernel's start-up fields fill the first two 64-byte lines");
+static_assert(offsetof(ActionArgs, nclass) < 64 && offsetof(ActionArgs, class_map) < 64 &&
+                  offsetof(ActionArgs, write_through) + sizeof(int) == 64,
+              "ActionArgs: the block-class fields ride in line 0, in the start-up's one batch of loads");
+constexpr int kClassMapSlot = 0x40;   // ActionArgs::class_map: class from the workgroup's CU slot
+constexpr int kClassMapShift = 0x3f;  //   ... else blockIdx.x >> (class_map & kClassMapShift)
+constexpr int kClassFlushUp = 0x100;  //   ... bit: flush one priority above the chain (A/B)
+constexpr int kMaxClasses = 3;        // chain priorities 2, 1, 0 under the prologue's 3
 
+// A/B build (-DLV_AB_KNOBS -> liblievae_hip_ab.so, its own instantiation objects): the
+// planner's environment knobs and, in the kernels, what only those knobs reach.  In the
+// product's tile kernel the fields below that no product plan varies (prio, task_spread,
+// ang_order, nclass, class_map, write_through 2) are compile-time constants -- the planner's
+// defaults -- so their branches, the second copy of the angle maths behind the prologue
+// barrier and the third copy of the flush are not in its code.
+//
 // Phase timestamps for tools/timeline.py (the A/B build's LV_STAMPS=1): lane 0 of each wave
 // writes the 100 MHz real-time counter at phase k, slot [block][wave < 16][k < 8].  Compiled
-// into the A/B library's kernels only (-DLV_AB_KNOBS, its own instantiation objects): the
-// product's kernels carry no stamp sites -- one of them was the first thing the tile kernel
-// did, a scalar test of a field the product always passes as null.
+// into the A/B library's kernels only: the product's kernels carry no stamp sites -- one of
+// them was the first thing the tile kernel did, a scalar test of a field the product always
+// passes as null.
 #ifdef LV_AB_KNOBS
-constexpr bool kStamps = true;
+constexpr bool kAbKnobs = true;
 #else
-constexpr bool kStamps = false;
+constexpr bool kAbKnobs = false;
 #endif
+constexpr bool kStamps = kAbKnobs;
+constexpr int kTilePrio = 2;  // ActionArgs::prio of every product plan
 constexpr int64_t kStampBlocks = 16384;
 __device__ __forceinline__ void phase_stamp(unsigned long long* st, int wave, int k) {
   if constexpr (kStamps) {
     if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampBlocks)
       st[((int64_t)blockIdx.x * 16 + wave) * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  }
+}
+// ... the forward tile kernel's block class + 1 (0 = classes off) in slot [block][15][0], and
+// each wave's hardware-ID register (SIMD in bits 5:4, CU 11:8, workgroup slot 19:16) in
+// slot [block][8 + wave][1]: a block has at most 8 waves, so waves 8-15's slots are free
+__device__ __forceinline__ void class_stamp(unsigned long long* st, int wave, int cls) {
+  if constexpr (kStamps) {
+    if (st && (threadIdx.x & 63) == 0 && blockIdx.x < kStampBlocks) {
+      if (wave == 0) st[((int64_t)blockIdx.x * 16 + 15) * 8] = (unsigned long long)(cls + 1);
+      if (wave < 8)
+        st[((int64_t)blockIdx.x * 16 + 8 + wave) * 8 + 1] =
+            0x100000000ull | __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));  // hwreg(HW_REG_HW_ID)
+    }
   }
 }
 // ... and at the end of each degree l of the chain, slot [block < 2048][wave][l < 24] after

@@ -233,10 +233,34 @@ __device__ __forceinline__ void tile_flush_rt(OutT* gout, const char* stage_b, i
                                               int write_through) {
   if (write_through == 1)
     tile_flush<OutT, 16>(gout, stage_b, mis, nbytes, (int)threadIdx.x, (int)blockDim.x);
-  else if (write_through == 2)
+  else if (kAbKnobs && write_through == 2)
     tile_flush<OutT, 0>(gout, stage_b, mis, nbytes, (int)threadIdx.x, (int)blockDim.x);
   else
     tile_flush<OutT, 1>(gout, stage_b, mis, nbytes, (int)threadIdx.x, (int)blockDim.x);
+}
+
+// s_setprio takes an immediate: p is wave-uniform (SGPR), so these are scalar branches around
+// one s_setprio each (a divergent guard would run the instruction in every wave).
+__device__ __forceinline__ void set_wave_prio(int p) {
+  if (p <= 0) __builtin_amdgcn_s_setprio(0);
+  else if (p == 1) __builtin_amdgcn_s_setprio(1);
+  else if (p == 2) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(3);
+}
+
+// Priority class of this block, 0 (favoured) .. nclass - 1, nclass 2 or 3; scalar arithmetic
+// on blockIdx.x or on the hardware-ID register, so wave-uniform.  Blocks are dealt round-
+// robin over the 8 XCDs and, within one, over its CUs: blockIdx.x >> 3 is the dealing round
+// and blockIdx.x >> log2(total CUs) counts the blocks a CU already holds when every block is
+// resident (the plan's condition for classes).  kClassMapSlot reads the workgroup's slot on
+// its CU instead: HW_ID (hardware register 4) bits 19:16, TG_ID, on GCN / CDNA parts.
+__device__ __forceinline__ int tile_block_class(int nclass, int class_map) {
+  constexpr int kHwIdTgId = 4 | (16 << 6) | ((4 - 1) << 11);  // hwreg(HW_REG_HW_ID, 16, 4)
+  unsigned x;
+  if (class_map & kClassMapSlot) x = __builtin_amdgcn_s_getreg(kHwIdTgId);
+  else x = blockIdx.x >> (class_map & kClassMapShift);
+  x = __builtin_amdgcn_readfirstlane(x);
+  return (int)(nclass == 2 ? (x & 1u) : x % 3u);
 }
 
 // Tile kernel.  One block = one sample group (Sw = 64 / C samples, one wave's lanes) x
@@ -283,14 +307,22 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   float* const aang = a.ang_out;
   const int64_t an = a.n;
   const int Sw = a.Sw;  // 64 / C, or fewer (plan: LDS per block vs blocks per CU)
-  const int prio = a.prio, spread = a.task_spread, transp = a.transpose;
-  const int ang_order = a.ang_order, wthrough = a.write_through;
+  // (the product's kernels hold the A/B-only fields as constants: action_common.h kAbKnobs)
+  const int prio = kAbKnobs ? a.prio : kTilePrio, spread = kAbKnobs ? a.task_spread : 0;
+  const int transp = a.transpose, wthrough = a.write_through;
+  const int ang_order = kAbKnobs ? a.ang_order : 0;
+  const int nclass = kAbKnobs ? a.nclass : 0, class_map = kAbKnobs ? a.class_map : 0;
   // this wave's degrees: a bit set (compile-time C: any set the planner balanced by cost);
   // run-time C keeps contiguous ranges [lo, hi) for its column-major spectrum slices
   const unsigned dmask = a.seg_mask[wave];
   const int nthr = (int)blockDim.x;
-  asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(prio), "s"(spread),
-               "s"(transp), "s"(ang_order), "s"(wthrough), "s"(dmask), "s"(nthr));
+  if constexpr (kAbKnobs)
+    asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(prio), "s"(spread),
+                 "s"(transp), "s"(ang_order), "s"(wthrough), "s"(nclass), "s"(class_map), "s"(dmask),
+                 "s"(nthr));
+  else
+    asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(transp),
+                 "s"(wthrough), "s"(dmask), "s"(nthr));
   // Wave priority (a.prio, the plan's default 2): the prologue (v / mu loads, exp -> ZYZ,
   // multiples, spectrum staging) issues at s_setprio 3 and the chain at 0, so on a CU that
   // holds blocks in different phases a new block's loads start ahead of the other blocks'
@@ -478,7 +510,22 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   block_sync_lds();
   phase_stamp(a.stamps, wave, 1);
 
-  if (prio >= 2) __builtin_amdgcn_s_setprio(0);
+  // Chain priority: 0 after the prologue's 3.  A/B (LV_TILE_NCLASS, plan_tile): with block
+  // classes the blocks that share a CU run their chains -- and flushes -- at priorities 2, 1,
+  // 0 by class.  Scheduling only; measured at config 2 it changes nothing, because VALU
+  // issue goes by priority and THEN AGE: at equal priority the block a CU received first
+  // already ends its chain ~0.9 us ahead of the second and that ~0.9 us ahead of the third
+  // (profiles/r08_timeline_block_classes.txt), the order the classes impose.  Not in the
+  // product's code.
+  int cprio = 0, cls = -1;
+  if (nclass > 1) {
+    cls = tile_block_class(nclass, class_map);
+    cprio = nclass - 1 - cls;
+  }
+  class_stamp(a.stamps, wave, cls);
+  if (cprio == 2) __builtin_amdgcn_s_setprio(2);
+  else if (cprio == 1) __builtin_amdgcn_s_setprio(1);
+  else if (prio >= 2) __builtin_amdgcn_s_setprio(0);
   if constexpr (kAngLate) {
     if ((dirs_lane || beta_lane) && !ang_early) write_ang();
   }
@@ -515,6 +562,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   phase_stamp(a.stamps, wave, 3);
   if (prio == 1) __builtin_amdgcn_s_setprio(3);  // A/B: the flush ahead of other waves' chains
   else if (prio == 3) __builtin_amdgcn_s_setprio(2);
+  else if (class_map & kClassFlushUp) set_wave_prio(cprio + 1);  // A/B: flush above the class's chain
   tile_flush_rt<OutT>(gout, stage_b, mis, Sv * (int)MC * (int)sizeof(OutT), wthrough);
   phase_stamp(a.stamps, wave, 4);
 }

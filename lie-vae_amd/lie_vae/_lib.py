@@ -45,8 +45,7 @@ _SIGS = {
     "lv_s2s2_bwd_f64": [_P, _P, _P, _P, _P, _I64, _P],
     "lv_wigner_d_fwd": [_P, _P, _I64, _I, _P],
     "lv_action_fwd_plan": [_I, _I64, _I, _I64, _I, _I, _P],
-    "lv_group_action_bwd_plan": [_I64, _I, _I, _I, _P],
-    "lv_group_action_fwd": [_P, _P, _I64, _P, _I, _I64, _I, _I, _I, _P],
+    "lv_group_action_bwd_plan": [_I64, _I, _I, _I, _P],    "lv_group_action_fwd": [_P, _P, _I64, _P, _I, _I64, _I, _I, _I, _P],
     "lv_group_action_bwd": [_P, _P, _I64, _P, _P, _P, _I64, _I, _I, _I, _P, _SZ, _P],
     "lv_exp_eazyz_vjp": [_P, _P, _P, _P, _P, _I64, _P],
     "lv_fused_exp_action_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _P, _SZ, _P],
@@ -105,7 +104,8 @@ _SIGS_EXTRA = {"lv_group_action_bwd_workspace": [_I64, _I, _I, _I], "lv_last_err
 EXPORTED = sorted(list(_SIGS) + list(_SIGS_EXTRA))
 # entry points of the A/B build only (liblievae_hip_ab.so, -DLV_AB_KNOBS; tools/ sweeps):
 # bound when the loaded library has them, never part of the product header
-_SIGS_AB = {"lv_deconv4s2_fwd_bf16_tile": [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, _P]}
+_SIGS_AB = {"lv_deconv4s2_fwd_bf16_tile": [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, _P],
+            "lv_ab_fwd_classes": [_I, _I64, _I, _I64, _I, _I, _I, _P]}
 
 _lib = None
 
@@ -166,6 +166,17 @@ def plan(kind, *args):
     d["seg_lo"] = [x for x in buf[7:24] if x >= 0]
     d["seg_mask"] = list(buf[24:24 + d["segments"]])
     return d
+
+
+def fwd_classes(fused, F_batch_stride, out_dtype, n, L, C, cus=0):
+    """Block priority classes of the forward's plan as a dict (A/B library only: the
+    product's kernels do not hold them; action.hip lv_ab_fwd_classes); no GPU call.  cus = 0:
+    the current device's compute units."""
+    if not hasattr(load(), "lv_ab_fwd_classes"):
+        raise LieVaeHipError("lv_ab_fwd_classes: an entry of the A/B library (liblievae_hip_ab.so)")
+    buf = (ctypes.c_int * 6)()
+    call("lv_ab_fwd_classes", fused, F_batch_stride, out_dtype, n, L, C, cus, buf)
+    return dict(zip(("tile", "nclass", "class_map", "off_nclass", "off_class_map", "off_seg_mask"), buf))
 
 
 def rotate_plan(N, C, H, W, flags=0):

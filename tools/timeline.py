@@ -3,7 +3,9 @@ LV_STAMPS=1: lane 0 of every wave writes the 100 MHz real-time counter at each p
 boundary; action_common.h phase_stamp).  For the last of R back-to-back launches of the
 fused forward and of lv_group_action_bwd at one shape, prints per degree segment (wave
 index) the median / 90th-percentile phase durations and, over the whole grid, when blocks
-start / finish relative to the earliest block start (10 ns ticks shown as us).
+start / finish relative to the earliest block start (10 ns ticks shown as us); for the
+forward also when the output drain starts and ends chip-wide against the launch time, the
+per-class chain ends under LV_TILE_NCLASS, each wave's SIMD and the blocks per CU.
 
   LIEVAE_HIP_LIB=lie-vae_amd/lie_vae/liblievae_hip_ab.so LV_STAMPS=1 \
       python tools/timeline.py [B] [L] [f32|bf16] [fwd|bwd|both]
@@ -57,7 +59,51 @@ def degree_costs(name, st, deg, nblk, masks):
     return res
 
 
-def report(name, st, nblk, nwave, phases, red=None, nred=0, extra=None):
+def drain(st, s, t0, nblk, launch_us):
+    """Forward tile kernel, chip-wide: when the output drain starts and ends (a block's flush
+    starts when its last wave leaves the second barrier, stamp 3, and ends at its last stamp 4)
+    against the launch time, the streamed-store time of the bytes, and -- with block priority
+    classes (slot [block][15][0] = class + 1) -- per class when the chains end."""
+    us = lambda x: x * TICK_US  # noqa: E731
+    chain_end = us(s[:, :, 2].max(axis=1) - t0)
+    fl0 = us(s[:, :, 3].max(axis=1) - t0)
+    fl1 = us(s[:, :, 4].max(axis=1) - t0)
+    print(f"  flush start  min/p10/50/90/max {fl0.min():6.2f} {np.percentile(fl0, 10):6.2f} {np.median(fl0):6.2f} "
+          f"{np.percentile(fl0, 90):6.2f} {fl0.max():6.2f} us")
+    print(f"  flush end    p10/50/90/max     {np.percentile(fl1, 10):6.2f} {np.median(fl1):6.2f} "
+          f"{np.percentile(fl1, 90):6.2f} {fl1.max():6.2f} us")
+    if launch_us:
+        print(f"  launch {launch_us:6.2f} us (events over the back-to-back launches, stamps on): "
+              f"last flush end -> launch end {launch_us - fl1.max():5.2f} us; "
+              f"first flush -> launch end {launch_us - fl0.min():5.2f} us")
+    cls = st[:nblk, 15, 0] - 1
+    if (cls >= 0).any():
+        for k in sorted(set(cls[cls >= 0].tolist())):
+            m = cls == k
+            print(f"  class {k} (s_setprio rank, 0 first): {int(m.sum()):4d} blocks  start {np.median(us(s[m, 0, 0] - t0)):5.2f}  "
+                  f"chain end p50/p90 {np.median(chain_end[m]):5.2f} {np.percentile(chain_end[m], 90):5.2f}  "
+                  f"flush start p50 {np.median(fl0[m]):5.2f}  flush end p50/max {np.median(fl1[m]):5.2f} {fl1[m].max():5.2f} us")
+    else:
+        print("  block classes off")
+    nwave = s.shape[1]
+    hw = st[:nblk, 8:8 + nwave, 1]
+    if (hw >> 32).all():  # each wave's hardware-ID register (class_stamp)
+        simd = (hw >> 4) & 3
+        print("  SIMD of wave k (blocks on SIMD 0/1/2/3): " +
+              "  ".join(f"w{w} " + "/".join(str(int((simd[:, w] == q).sum())) for q in range(4)) for w in range(nwave)))
+        # blocks b and b + 8 share an XCD; within it SE / SH / CU id name the CU
+        cu = (np.arange(nblk) % 8) * 4096 + ((hw[:, 0] >> 8) & 0xff)
+        _, inv, cnt = np.unique(cu, return_inverse=True, return_counts=True)
+        print("  CUs holding 1/2/3/4+ blocks: " + " ".join(str(int((cnt == k).sum())) for k in (1, 2, 3)) +
+              f" {int((cnt >= 4).sum())}")
+        for k in (1, 2, 3):
+            m = cnt[inv] == k
+            if m.any():
+                print(f"    blocks on a CU with {k}: chain end p50/max {np.median(chain_end[m]):5.2f} {chain_end[m].max():5.2f}  "
+                      f"flush end p50/max {np.median(fl1[m]):5.2f} {fl1[m].max():5.2f} us")
+
+
+def report(name, st, nblk, nwave, phases, red=None, nred=0, extra=None, launch_us=None):
     s = st[:nblk, :nwave, :]
     t0 = s[:, :, 0][s[:, :, 0] > 0].min()
     print(f"== {name}: {nblk} blocks x {nwave} waves")
@@ -82,6 +128,8 @@ def report(name, st, nblk, nwave, phases, red=None, nred=0, extra=None):
                                             for w in range(nwave)) + " us after wave start")
     first = [us(np.median(s[:, w, 1] - t0)) for w in range(nwave)]
     print("  median time of phase 1 end per wave (from grid start): " + " ".join(f"{x:5.2f}" for x in first))
+    if phases[-1] == "flush":
+        drain(st, s, t0, nblk, launch_us)
     if red is not None and nred:
         r = red[:nred]
         print(f"  reduce kernel: start p50 {us(np.median(r[:, 0] - t0)):6.2f}  end max {us(r[:, 1].max() - t0):6.2f} us"
@@ -108,14 +156,21 @@ def main():
     code = _lib.LV_DTYPE_BF16 if dt == "bf16" else _lib.LV_DTYPE_F32
     assert lib.lv_action_fwd_plan(1, 0, code, B, L, C, plan) == 0
     if which in ("fwd", "both"):
-        for _ in range(R):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for r in range(2 * R):
+            if r == R:  # the first R warm up; the second R are timed
+                ev[0].record()
             assert lib.lv_fused_exp_action_fwd(None, P(v), P(F), 0, P(out), code, P(ang), B, L, C, 0, None) == 0
+        ev[1].record()
+        torch.cuda.synchronize()
+        launch_us = ev[0].elapsed_time(ev[1]) * 1e3 / R
         st, _, deg = stamps(lib, True)
         print(f"plan: blocks {plan[1]} segments {plan[2]} lds {plan[4]} degree sets "
               f"{[bin(plan[24 + k]) for k in range(plan[2])]}")
         report(f"fused forward B={B} l={L} {dt}", st, min(plan[1], KB), plan[2],
                ["start", "prologue", "chain", "barrier", "flush"],
-               extra=[(5, "loads landed"), (6, "exp->ZYZ done (wave 0)"), (7, "multiples done (wave 0)")])
+               extra=[(5, "loads landed"), (6, "exp->ZYZ done (wave 0)"), (7, "multiples done (wave 0)")],
+               launch_us=launch_us)
         degree_costs("forward", st, deg, plan[1], [plan[24 + k] for k in range(plan[2])])
     if which in ("bwd", "both"):
         lib.lv_fused_exp_action_fwd(None, P(v), P(F), 0, P(out), _lib.LV_DTYPE_F32, P(ang), B, L, C, 0, None)
