@@ -129,8 +129,28 @@ int lv_s2s2_bwd_f64(const double* v1, const double* v2, const double* gR, double
 
 /* ---- wigner_d_matrix for l = 0..L, packed: lie_tools.py:211-223 (a9) -------
  * ang (n,3) -> D (n, sum_l (2l+1)^2), block l row-major at offset
- * sum_{k<l}(2k+1)^2.  Parity/debug entry point; the hot path never materialises D. */
+ * sum_{k<l}(2k+1)^2.  One launch per degree.  The decoder's hot path never materialises
+ * D (it applies the factors to the spectrum, a10 below); these entry points serve code
+ * written against D itself, and are differentiable in the angles like the reference's
+ * tensor expression.  l or L outside 0..LV_MAX_DEGREE, n < 0, an n whose grid would not
+ * fit one launch, or (with n > 0) a null pointer return LV_ERR_ARG before anything runs. */
 int lv_wigner_d_fwd(const float* ang, float* D, int64_t n, int L, void* stream);
+/* VJP of the above: gD (n, sum_l (2l+1)^2) -> gang (n,3).  The per-degree kernels of
+ * lv_wigner_d_block_bwd run for l = 0..L in ascending order on the stream; degree 0 writes
+ * gang and each later degree adds to it in place (one owning thread per element): a fixed
+ * summation order, no atomics, no workspace. */
+int lv_wigner_d_bwd(const float* ang, const float* gD, float* gang, int64_t n, int L, void* stream);
+/* D_l only: ang (n,3) -> D (n, 2l+1, 2l+1) row-major, one launch; bit for bit block l of
+ * lv_wigner_d_fwd. */
+int lv_wigner_d_block_fwd(const float* ang, float* D, int64_t n, int l, void* stream);
+/* VJP of lv_wigner_d_block_fwd: gD (n, 2l+1, 2l+1) -> gang (n,3).  One lane per (sample,
+ * column q) recomputes the chain on e_q and contracts it with gD[s, :, q]; the 2l+1 column
+ * partials of a sample are added in ascending q inside the kernel.  A sample's gradient
+ * depends only on its own angles and gD -- not on n, its position in the batch or the grid --
+ * so it is bitwise reproducible and bitwise equal to the same sample run alone.  Exactly
+ * zero at l = 0. */
+int lv_wigner_d_block_bwd(const float* ang, const float* gD, float* gang, int64_t n, int l,
+                          void* stream);
 
 /* ---- block_wigner_matrix_multiply: lie_tools.py:226-253 (a10) --------------
  * out[s, l^2 + i, c] = sum_j D_l(ang[s])[i,j] (or D^T if transpose) F[s, l^2 + j, c]

@@ -21,6 +21,11 @@ LV_EXTERN_BWD(5) LV_EXTERN_BWD(6) LV_EXTERN_BWD(7) LV_EXTERN_BWD(8) LV_EXTERN_BW
 LV_EXTERN_BWD(10) LV_EXTERN_BWD(11) LV_EXTERN_BWD(12) LV_EXTERN_BWD(13) LV_EXTERN_BWD(14)
 LV_EXTERN_BWD(15) LV_EXTERN_BWD(16) LV_EXTERN_BWD(17) LV_EXTERN_BWD(18) LV_EXTERN_BWD(19)
 LV_EXTERN_BWD(20)
+LV_EXTERN_WIG_BWD(0) LV_EXTERN_WIG_BWD(1) LV_EXTERN_WIG_BWD(2) LV_EXTERN_WIG_BWD(3) LV_EXTERN_WIG_BWD(4)
+LV_EXTERN_WIG_BWD(5) LV_EXTERN_WIG_BWD(6) LV_EXTERN_WIG_BWD(7) LV_EXTERN_WIG_BWD(8) LV_EXTERN_WIG_BWD(9)
+LV_EXTERN_WIG_BWD(10) LV_EXTERN_WIG_BWD(11) LV_EXTERN_WIG_BWD(12) LV_EXTERN_WIG_BWD(13) LV_EXTERN_WIG_BWD(14)
+LV_EXTERN_WIG_BWD(15) LV_EXTERN_WIG_BWD(16) LV_EXTERN_WIG_BWD(17) LV_EXTERN_WIG_BWD(18) LV_EXTERN_WIG_BWD(19)
+LV_EXTERN_WIG_BWD(20)
 
 // Shared-spectrum gradient: gF[e] = sum over the tile kernel's slabs.  (Round-2 kernel,
 // kept for A/B as LV_BWD_REDUCE=1; action_bwd_reduce2_kernel below is the default.)  One block per
@@ -679,6 +684,20 @@ constexpr std::array<int (*)(Args&), sizeof...(Is)> launcher_table(std::integer_
 }
 constexpr auto kBwdRun = launcher_table<BwdLauncher, BwdLaunch>(std::make_integer_sequence<int, LV_MAX_DEGREE + 1>{});
 constexpr auto kWigRun = launcher_table<WigLauncher, WigLaunch>(std::make_integer_sequence<int, LV_MAX_DEGREE + 1>{});
+constexpr auto kWigBwdRun = launcher_table<WigBwdLauncher, WigBwdLaunch>(std::make_integer_sequence<int, LV_MAX_DEGREE + 1>{});
+
+// Argument checks of the Wigner-D entry points (host only: before any launch or pointer
+// use).  The grids are one thread per (sample, column) forward and whole samples per block
+// backward; both must fit a launch's 2^31 - 1 blocks at the largest degree the call runs.
+constexpr int64_t kMaxGridX = 0x7fffffff;
+int check_wigner(int64_t n, int l, const char* lname, bool bwd) {
+  LV_CHECK_ARG(n >= 0, "n must be >= 0 (got %lld)", (long long)n);
+  LV_CHECK_ARG(l >= 0 && l <= LV_MAX_DEGREE, "%s must be in [0, %d] (got %d)", lname, LV_MAX_DEGREE, l);
+  const int64_t nmax = bwd ? kMaxGridX * wig_bwd_samples_rt(l) : kMaxGridX * kWigThreads / (2 * l + 1);
+  LV_CHECK_ARG(n <= nmax, "n = %lld is too large for one launch at degree %d (at most %lld)", (long long)n, l,
+               (long long)nmax);
+  return LV_OK;
+}
 
 // Backward plan (action_bwd_tile_kernel): samples per block (Sw <= 64/C, reduced until the
 // fp32 gradient tile fits), degree segments as in the forward (the backward chain costs
@@ -1109,13 +1128,44 @@ int lv_compute_units(void) { return device_cus(); }
 
 int lv_wigner_d_fwd(const float* ang, float* D, int64_t n, int L, void* stream) {
   clear_error();
-  LV_CHECK_ARG(n >= 0, "n must be >= 0");
-  LV_CHECK_ARG(L >= 0 && L <= LV_MAX_DEGREE, "l_max out of range");
+  if (int e = check_wigner(n, L, "l_max", false)) return e;
   if (n == 0) return LV_OK;
   LV_CHECK_ARG(ang && D, "null pointer");
-  WigLaunch p{ang, D, n, (L + 1) * (2 * L + 1) * (2 * L + 3) / 3, (hipStream_t)stream};
+  WigLaunch p{ang, D, n, wigner_block_off(L + 1), true, (hipStream_t)stream};
   for (int l = 0; l <= L; ++l)
     if (int e = kWigRun[l](p)) return e;
+  return LV_OK;
+}
+
+int lv_wigner_d_block_fwd(const float* ang, float* D, int64_t n, int l, void* stream) {
+  clear_error();
+  if (int e = check_wigner(n, l, "l", false)) return e;
+  if (n == 0) return LV_OK;
+  LV_CHECK_ARG(ang && D, "null ang / D");
+  WigLaunch p{ang, D, n, (int64_t)(2 * l + 1) * (2 * l + 1), false, (hipStream_t)stream};
+  return kWigRun[l](p);
+}
+
+int lv_wigner_d_block_bwd(const float* ang, const float* gD, float* gang, int64_t n, int l, void* stream) {
+  clear_error();
+  if (int e = check_wigner(n, l, "l", true)) return e;
+  if (n == 0) return LV_OK;
+  LV_CHECK_ARG(ang && gD && gang, "null ang / gD / gang");
+  WigBwdLaunch p{ang, gD, gang, n, (int64_t)(2 * l + 1) * (2 * l + 1), false, false, (hipStream_t)stream};
+  return kWigBwdRun[l](p);
+}
+
+int lv_wigner_d_bwd(const float* ang, const float* gD, float* gang, int64_t n, int L, void* stream) {
+  clear_error();
+  if (int e = check_wigner(n, L, "l_max", true)) return e;
+  if (n == 0) return LV_OK;
+  LV_CHECK_ARG(ang && gD && gang, "null ang / gD / gang");
+  // ascending degrees on the stream: degree 0 writes gang, each later one adds in place
+  WigBwdLaunch p{ang, gD, gang, n, wigner_block_off(L + 1), true, false, (hipStream_t)stream};
+  for (int l = 0; l <= L; ++l) {
+    p.accumulate = l > 0;
+    if (int e = kWigBwdRun[l](p)) return e;
+  }
   return LV_OK;
 }
 

@@ -7,7 +7,8 @@
 //   lv_group_action_fwd      block_wigner_matrix_multiply, lie_tools.py:226-253
 //   lv_fused_exp_action_fwd  mu@rodrigues(v) -> ZYZ -> block D·F in one pass
 //                            (reparameterize.py:269-273, vae.py:182, decoders.py:47-56)
-//   lv_wigner_d_fwd          packed D_l blocks (parity / debug only)
+//   lv_wigner_d_fwd          packed D_l blocks 0..L; lv_wigner_d_block_fwd: D_l alone
+//                            (their VJPs: wigner_bwd.h)
 //
 // Two forward kernels:
 //   * action_fwd_tile_kernel (shared spectrum, LDS tile fits): one block per sample
@@ -575,9 +576,11 @@ __global__ __launch_bounds__(512) void action_fwd_tile_kernel(ActionArgs a) {
 
 // ------------------------------------------------------------ Wigner-D blocks
 // Column q of D_l = chain applied to e_q; one thread per (sample, q), one kernel per
-// degree.  D is (n, dsz) with block l row-major at offset off.
+// degree.  Sample s's block goes to D + s * pitch + off, row-major: the packed layout
+// (pitch = sum_k (2k+1)^2, off = sum_{k<l} (2k+1)^2) or the block alone (pitch =
+// (2l+1)^2, off = 0) -- the same values either way, only the destination differs.
 template <int l>
-__global__ void wigner_d_kernel(const float* ang, float* D, int64_t n, int dsz) {
+__global__ void wigner_d_kernel(const float* ang, float* D, int64_t n, int64_t pitch, int off) {
   constexpr int nn = 2 * l + 1;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= n * nn) return;
@@ -594,8 +597,7 @@ __global__ void wigner_d_kernel(const float* ang, float* D, int64_t n, int dsz) 
   xrot<l, 1>(t, x, y);
   jmul<l>(y, x);
   xrot<l, 0>(t, x, y);
-  constexpr int off = l * (2 * l - 1) * (2 * l + 1) / 3;  // sum_{k<l} (2k+1)^2
-  sfor<nn>([&](auto I) { D[s * dsz + off + LV_CV(I) * nn + q] = y[LV_CV(I)]; });
+  sfor<nn>([&](auto I) { D[s * pitch + off + LV_CV(I) * nn + q] = y[LV_CV(I)]; });
 }
 
 // ------------------------------------------------------------------ host side
@@ -683,11 +685,16 @@ int FwdLauncher<LT>::run(FwdLaunch& p) {
   LV_RETURN_LAUNCH("action_fwd_kernel");
 }
 
+// Offset of block l in the packed row: sum_{k<l} (2k+1)^2.
+__host__ __device__ constexpr int wigner_block_off(int l) { return l * (2 * l - 1) * (2 * l + 1) / 3; }
+constexpr int kWigThreads = 256;
+
 struct WigLaunch {
   const float* ang;
   float* D;
   int64_t n;
-  int dsz;
+  int64_t pitch;  // floats per sample of D
+  bool packed;    // block l at wigner_block_off(l) of the row, else at 0
   hipStream_t stream;
 };
 
@@ -698,8 +705,8 @@ struct WigLauncher {
 template <int l>
 int WigLauncher<l>::run(WigLaunch& p) {
   const int64_t total = p.n * (2 * l + 1);
-  hipLaunchKernelGGL((wigner_d_kernel<l>), dim3(ceil_div(total, 256)), dim3(256), 0, p.stream,
-                     p.ang, p.D, p.n, p.dsz);
+  hipLaunchKernelGGL((wigner_d_kernel<l>), dim3(ceil_div(total, kWigThreads)), dim3(kWigThreads), 0,
+                     p.stream, p.ang, p.D, p.n, p.pitch, p.packed ? wigner_block_off(l) : 0);
   LV_RETURN_LAUNCH("wigner_d_kernel");
 }
 

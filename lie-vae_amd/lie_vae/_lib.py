@@ -44,6 +44,9 @@ _SIGS = {
     "lv_s2s2_fwd_f64": [_P, _P, _P, _I64, _P],
     "lv_s2s2_bwd_f64": [_P, _P, _P, _P, _P, _I64, _P],
     "lv_wigner_d_fwd": [_P, _P, _I64, _I, _P],
+    "lv_wigner_d_bwd": [_P, _P, _P, _I64, _I, _P],
+    "lv_wigner_d_block_fwd": [_P, _P, _I64, _I, _P],
+    "lv_wigner_d_block_bwd": [_P, _P, _P, _I64, _I, _P],
     "lv_action_fwd_plan": [_I, _I64, _I, _I64, _I, _I, _P],
     "lv_group_action_bwd_plan": [_I64, _I, _I, _I, _P],    "lv_group_action_fwd": [_P, _P, _I64, _P, _I, _I64, _I, _I, _I, _P],
     "lv_group_action_bwd": [_P, _P, _I64, _P, _P, _P, _I64, _I, _I, _I, _P, _SZ, _P],

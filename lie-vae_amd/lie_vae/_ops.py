@@ -367,14 +367,51 @@ def fused_exp_action(mu, v, spectrum, L, transpose=False, out_dtype=F32):
     return _FusedExpAction.apply(mu, v, _f32c(spectrum), L, transpose, out_dtype)
 
 
+class _WignerD(torch.autograd.Function):
+    """angles (n, 3) -> D: one degree's block (n, (2l+1)^2) or the packed blocks 0..L
+    (n, sum (2l+1)^2).  fp32 whatever the input dtype; the angle gradient comes back in the
+    input's dtype, with the values computed in fp32."""
+
+    @staticmethod
+    def forward(ctx, angles, l, packed):
+        a = _prep(angles)
+        n = a.shape[0]
+        width = (l + 1) * (2 * l + 1) * (2 * l + 3) // 3 if packed else (2 * l + 1) ** 2
+        D = _empty((n, width), a)
+        call("lv_wigner_d_fwd" if packed else "lv_wigner_d_block_fwd", ptr(a), ptr(D), n, l,
+             _lib.stream_of(a.device))
+        ctx.save_for_backward(a)
+        ctx.l, ctx.packed, ctx.in_dtype = l, packed, angles.dtype
+        return D
+
+    @staticmethod
+    def backward(ctx, gD):
+        (a,) = ctx.saved_tensors
+        gD = _prep(gD)  # contiguous fp32: the upstream may be a transposed view
+        gang = torch.empty_like(a)
+        call("lv_wigner_d_bwd" if ctx.packed else "lv_wigner_d_block_bwd", ptr(a), ptr(gD),
+             ptr(gang), a.shape[0], ctx.l, _lib.stream_of(a.device))
+        return gang.to(ctx.in_dtype), None, None
+
+
+def _check_angles(angles, what):
+    assert angles.dim() == 2 and angles.shape[1] == 3, \
+        f"{what}: angles must be (n,3), got {tuple(angles.shape)}"
+    _lib.require_device(angles)
+
+
 def wigner_blocks(angles, L):
-    """Packed D_0..D_L for each angle triple (debug / parity), (n, sum (2l+1)^2)."""
-    angles = _prep(angles)
-    n = angles.shape[0]
-    tot = (L + 1) * (2 * L + 1) * (2 * L + 3) // 3
-    D = _empty((n, tot), angles)
-    call("lv_wigner_d_fwd", ptr(angles), ptr(D), n, L, stream())
-    return D
+    """Packed D_0..D_L for each angle triple, (n, sum (2l+1)^2); differentiable in the
+    angles (lv_wigner_d_bwd)."""
+    _check_angles(angles, "wigner_blocks")
+    return _WignerD.apply(angles, L, True)
+
+
+def wigner_block(angles, l):
+    """D_l alone for each angle triple, (n, (2l+1)^2) row-major, in one launch;
+    differentiable in the angles (lv_wigner_d_block_bwd)."""
+    _check_angles(angles, "wigner_block")
+    return _WignerD.apply(angles, l, False)
 
 
 # ------------------------------------------------------ encoder regularisers

@@ -100,14 +100,12 @@ def quaternions_to_group_matrix(q):
 def wigner_d_matrix(angles, degree):
     """D_l(α,β,γ) = X(α)·J·X(β)·J·X(γ), (...,3) -> (...,2l+1,2l+1) — lie_tools.py:211-223.
 
-    Materialises D (debug / parity use); the decoder path never does."""
+    Materialises D_l in one launch (the decoder path never forms D) and is differentiable
+    in the angles, like the reference's tensor expression; fp32 for any input dtype."""
     assert angles.shape[-1] == 3, 'Input must be 3 dim vectors'
     lead = angles.shape[:-1]
-    a = angles.reshape(-1, 3)
     n = 2 * degree + 1
-    D = _ops.wigner_blocks(a, degree)
-    off = degree * (2 * degree - 1) * (2 * degree + 1) // 3
-    return D[:, off:off + n * n].reshape(*lead, n, n)
+    return _ops.wigner_block(angles.reshape(-1, 3), degree).reshape(*lead, n, n)
 
 
 def block_wigner_matrix_multiply(angles, spectrum, max_degree, transpose=False):
