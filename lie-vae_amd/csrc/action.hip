@@ -27,185 +27,13 @@ LV_EXTERN_WIG_BWD(10) LV_EXTERN_WIG_BWD(11) LV_EXTERN_WIG_BWD(12) LV_EXTERN_WIG_
 LV_EXTERN_WIG_BWD(15) LV_EXTERN_WIG_BWD(16) LV_EXTERN_WIG_BWD(17) LV_EXTERN_WIG_BWD(18) LV_EXTERN_WIG_BWD(19)
 LV_EXTERN_WIG_BWD(20)
 
-// Shared-spectrum gradient: gF[e] = sum over the tile kernel's slabs.  (Round-2 kernel,
-// kept for A/B as LV_BWD_REDUCE=1; action_bwd_reduce2_kernel below is the default.)  One block per
-// kBwdReduceCols consecutive elements, lane = (slab stream k, column); the block's 16
-// waves split the slabs into contiguous runs, and inside a run stream k takes every
-// kBwdReduceStreams-th slab (64-byte loads, unrolled).  Against one element per lane this
-// is 4x fewer serial loads per lane and 4x the blocks (76 at l = 10, C = 10): 5.1 -> 4.4 us
-// at batch 4096.  Partials are added in a fixed order (run, then stream): deterministic.
-#ifndef LV_REDUCE_COLS
-#define LV_REDUCE_COLS 16
-#endif
-constexpr int kBwdReduceCols = LV_REDUCE_COLS;
-constexpr int kBwdReduceStreams = 64 / kBwdReduceCols;
-__global__ __launch_bounds__(64 * kBwdReduceWaves) void action_bwd_reduce_kernel(
-    const float* ws_F, float* gF, int64_t MC, int nslab) {
-  __shared__ float part[kBwdReduceWaves][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int k = lane / kBwdReduceCols, col = lane - k * kBwdReduceCols;
-  const int64_t e = (int64_t)blockIdx.x * kBwdReduceCols + col;
-  const int per = (nslab + kBwdReduceWaves - 1) / kBwdReduceWaves;
-  const int b0 = min(nslab, w * per), b1 = min(nslab, b0 + per);
-  float sum = 0.f;
-  if (e < MC) {
-    int b = b0 + k;
-    constexpr int S = kBwdReduceStreams;
-    for (; b + 7 * S < b1; b += 8 * S) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ws_F[(int64_t)(b + u * S) * MC + e];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sum += v[u];
-    }
-    for (; b < b1; b += S) sum += ws_F[(int64_t)b * MC + e];
-  }
-  part[w][lane] = sum;
-  __syncthreads();
-  if (threadIdx.x < kBwdReduceCols && e < MC) {
-    float r = 0.f;
-    for (int ww = 0; ww < kBwdReduceWaves; ++ww) {
-      float rw = part[ww][col];
-#pragma unroll
-      for (int kk = 1; kk < kBwdReduceStreams; ++kk) rw += part[ww][kk * kBwdReduceCols + col];
-      r += rw;
-    }
-    gF[e] = r;
-  }
-}
-
-// The default since round 3: one block per COLS consecutive elements, 1024
-// threads = 1024/COLS slab streams per element; stream k sums slabs k, k + S, k + 2S, ...
-// (all of a thread's loads issued together), then the S partials of an element are
-// added by a fixed-order halving tree in LDS.  Deterministic; a different (fixed)
-// summation order from action_bwd_reduce_kernel.
-template <int COLS>
-__global__ __launch_bounds__(1024) void action_bwd_reduce2_kernel(const float* ws_F, float* gF, int64_t MC,
-                                                                  int nslab) {
-  constexpr int S = 1024 / COLS;
-  __shared__ float part[S][COLS];
-  const int col = (int)threadIdx.x % COLS, k = (int)threadIdx.x / COLS;
-  const int64_t e = (int64_t)blockIdx.x * COLS + col;
-  float sum = 0.f;
-  if (e < MC) {
-    int b = k;
-    for (; b + 7 * S < nslab; b += 8 * S) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ws_F[(int64_t)(b + u * S) * MC + e];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sum += v[u];
-    }
-    for (; b < nslab; b += S) sum += ws_F[(int64_t)b * MC + e];
-  }
-  part[k][col] = sum;
-#pragma unroll
-  for (int h = S / 2; h >= 1; h >>= 1) {
-    __syncthreads();
-    if (k < h) part[k][col] += part[k + h][col];
-  }
-  if (k == 0 && e < MC) gF[e] = part[0][col];
-}
-
-// Chunk-major slabs (ActionBwdArgs::slab_chunked): one block per 16-element chunk, whose
-// gx slabs are one contiguous run of gx * 64 bytes.  Thread t takes quarter q = t % 4 of
-// every slab b = t / 4, t / 4 + 256, ... (16-byte loads, all issued together), then the 256
-// partials of each quarter are added by a fixed-order halving tree.  Deterministic.
-__global__ __launch_bounds__(1024) void action_bwd_reduce3_kernel(const float* ws_F, float* gF, int64_t MC,
-                                                                  int nslab, unsigned long long* stamps) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  unsigned long long* rst = kStamps && stamps ? stamps + kStampBlocks * 16 * 8 + 2 * (int64_t)blockIdx.x : nullptr;
-  if (rst && threadIdx.x == 0) rst[0] = __builtin_amdgcn_s_memrealtime();
-  __shared__ f4 part[256][4];
-  const int q = (int)threadIdx.x & 3, bs = (int)threadIdx.x >> 2;
-  const f4* base = reinterpret_cast<const f4*>(ws_F + (int64_t)blockIdx.x * nslab * kSlabChunk) + q;
-  f4 acc = {0.f, 0.f, 0.f, 0.f};
-  int b = bs;
-  for (; b + 3 * 256 < nslab; b += 4 * 256) {
-    f4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = base[(int64_t)(b + u * 256) * 4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc += v[u];
-  }
-  {
-    f4 v[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) v[u] = b + u * 256 < nslab ? base[(int64_t)(b + u * 256) * 4] : f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-      if (b + u * 256 < nslab) acc += v[u];
-  }
-  part[bs][q] = acc;
-#pragma unroll
-  for (int h = 128; h >= 1; h >>= 1) {
-    __syncthreads();
-    if (bs < h) part[bs][q] += part[bs + h][q];
-  }
-  if (bs == 0) {
-    const f4 r = part[0][q];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t e = (int64_t)blockIdx.x * kSlabChunk + 4 * q + k;
-      if (e < MC) gF[e] = r[k];
-    }
-    if (rst) rst[1] = __builtin_amdgcn_s_memrealtime();
-  }
-}
-
-// Chunk-major slabs, fewer barriers: as action_bwd_reduce3_kernel, but the 16 slab streams
-// of a wave are combined by cross-lane shuffles (xor 4, 8, 16, 32: stream pairs, no
-// barrier), then the 16 waves' partials by one barrier and a 16-term sum in wave order.
-// Deterministic (a fixed order, different from reduce3's halving tree).
-__global__ __launch_bounds__(1024) void action_bwd_reduce4_kernel(const float* ws_F, float* gF, int64_t MC,
-                                                                  int nslab) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __shared__ f4 part[16][4];
-  const int q = (int)threadIdx.x & 3, bs = (int)threadIdx.x >> 2;
-  const f4* base = reinterpret_cast<const f4*>(ws_F + (int64_t)blockIdx.x * nslab * kSlabChunk) + q;
-  f4 acc = {0.f, 0.f, 0.f, 0.f};
-  int b = bs;
-  for (; b + 3 * 256 < nslab; b += 4 * 256) {
-    f4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = base[(int64_t)(b + u * 256) * 4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc += v[u];
-  }
-  {
-    f4 v[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) v[u] = b + u * 256 < nslab ? base[(int64_t)(b + u * 256) * 4] : f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-      if (b + u * 256 < nslab) acc += v[u];
-  }
-#pragma unroll
-  for (int m = 4; m <= 32; m <<= 1) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
-  }
-  const int w = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-  if (lane < 4) part[w][lane] = acc;
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    f4 r = part[0][q];
-#pragma unroll
-    for (int ww = 1; ww < 16; ++ww) r += part[ww][q];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t e = (int64_t)blockIdx.x * kSlabChunk + 4 * q + k;
-      if (e < MC) gF[e] = r[k];
-    }
-  }
-}
-
-// Chunk-major slabs, one 256-thread block per 16-element chunk (the default, LV_BWD_REDUCE=6):
-// thread t takes quarter q = t % 4 of slabs t / 4, t / 4 + 64, ... -- up to kR5Loads 16-byte
-// loads issued together per round -- then the 64 streams of a quarter are combined by
-// cross-lane shuffles inside each wave (xor 4, 8, 16, 32) and the 4 waves' partials in wave
-// order after one barrier.  Fewer threads and barriers than reduce3 (1,024 threads, an
-// 8-level tree); deterministic in a fixed order of its own.
+// Shared-spectrum gradient: gF[e] = sum over the backward kernels' dF slabs.
+// Chunk-major slabs (action_bwd.h), one 256-thread block per 16-element chunk, whose gx slabs
+// are one contiguous run of gx * 64 bytes: thread t takes quarter q = t % 4 of slabs t / 4,
+// t / 4 + 64, ... -- up to kR5Loads 16-byte loads issued together per round -- then the 64
+// streams of a quarter are combined by cross-lane shuffles inside each wave (xor 4, 8, 16, 32)
+// and the 4 waves' partials in wave order after one barrier.  Deterministic in a fixed order.
+// (Its four predecessors: DESIGN.md, "retired backward variants".)
 constexpr int kR5Loads = 12;
 // The reduce5 body for one chunk: the modular reduce and the fused VJP launch's reduce blocks
 // both call it, so their dF is the same fixed summation order by construction (the bitwise
@@ -417,7 +245,7 @@ constexpr int64_t kWriteThroughMaxBytes = 32ll << 20;
 // A/B knobs (LV_TILE=0 disables the tile kernel, LV_TILE_WT=0/1 forces the store policy,
 // LV_*_NSEG force segment counts, LV_BWD_FGLOBAL forces the backward's global-spectrum
 // mode) exist only in the A/B build (-DLV_AB_KNOBS -> liblievae_hip_ab.so, used by
-// tools/ and one bitwise test): the product library never reads the environment, so a
+// tools/ and the bitwise tests): the product library never reads the environment, so a
 // stray variable cannot change its kernels or its summation order.
 #ifdef LV_AB_KNOBS
 int env_int(const char* name, int dflt) {
@@ -735,27 +563,6 @@ int device_cus() {
   cache[dev].store(cus, std::memory_order_relaxed);
   return cus;
 }
-// LV_BWD_REDUCE default (see action_bwd_common): 6 = chunk-major slabs + reduce5 (one
-// 256-thread block per 16-element chunk).  Same box, backward alone (profiles/r05_reduce_ab.txt):
-// 512: 8.93 -> 8.72 us, 4,096: 14.45 -> 13.94, 16,384: 32.2 -> 31.9, 65,536: 103.4 -> 102.5
-// against reduce3; a block per quarter chunk (4x the blocks, 16-byte reads at a 64-byte
-// stride) was slower: 4,096: 17.2 us.
-constexpr int kBwdReduceDefault = 6;
-// LV_BWD_VARIANT default (kBwdVar* bits): JIT chain (profiles/r04_bwd_reduce_ab.txt); the
-// persistent kernel with one tile buffer at 3 blocks per CU (65,536: 131 -> 114 us against
-// the double-buffered 2 blocks per CU, profiles/r05_ab4.txt), its next multiples filled by
-// one wave (profiles/r05_ab8.txt), its angle partials summed by one wave from LDS instead of
-// a cross-lane tree on every wave (round 6, same box: 65,536 104.0 -> 96.8 us, 262,144 378
-// -> 358, 16,384 31.9 -> 30.6; the padded tile, kBwdVarPersistPad, was slower alone and
-// with it: 104.5 / 100.2-100.9 us, profiles/r06_ab_persist.txt), and its gradient tile
-// by buffer loads to LDS with SGPR round offsets (65,536 99.2-100.5 -> 96.8-97.5 us,
-// 4,096 13.7-13.9 -> 13.3-13.5, 262,144 359-360 -> 351-352; profiles/r06_ab_bufdma.txt),
-// and its dF slab as 16-byte write-through stores (4,096 13.47-13.52 -> 12.92-13.03 us,
-// 16,384 29.9-30.3 -> 29.4-29.5, 2,048 10.4 -> 10.25, 65,536 unchanged; dF bitwise equal;
-// profiles/r06_ab_slabwt.txt)
-constexpr int kBwdVariantDefault = kBwdVarJit | kBwdVarPersistSingle | kBwdVarPersistTask1 | kBwdVarPersistAng |
-                                   kBwdVarPersistBufDma | kBwdVarPersistSlabWT;
-
 // Fallback for tiles that leave no LDS room for the spectrum and the dF slab (large C at
 // high l): the whole CU's LDS, the spectrum read from global memory and the slab kept in
 // the block's workspace row (kBwdFSharedGlobal); per-sample spectra only need the bigger
@@ -766,7 +573,7 @@ constexpr int64_t kBwdMaxBlocksFallback = 1024;
 struct BwdPlan {
   int Sw, nseg, gx, fpitch, fmode;
   int persist;            // action_bwd_persist_kernel
-  size_t ws_gang_off;     // persist: byte offset of the angle-gradient region (fused VJP)
+  size_t ws_gang_off;     // byte offset of the workspace's angle-gradient region (fused VJP)
   int64_t groups;
   int seg_lo[kMaxSeg + 1];
   unsigned seg_mask[kMaxSeg];
@@ -777,7 +584,7 @@ struct BwdPlan {
 // groups = 1,537 samples on MI355X): up to 3 blocks per CU walk the groups, the next
 // group's multiples prefetched, one dF slab per block.  Round 5 used it only beyond one
 // round of 3 blocks per CU (769 groups; 4,096: 14.26 vs 14.47 us one-group vs persistent,
-// profiles/r05_bwd_persist_ab2.txt); with the LDS angle sums it is faster from 342 groups:
+// profiles/r05_bwd_persist_ab2.txt); with the round-6 LDS angle sums it is faster from 342 groups:
 // 2,048 samples 11.15 -> 10.5 us, 4,096 14.1 -> 13.8, while at <= one group per CU the
 // one-group kernel's 8 segments keep more waves busy (512: 8.5 vs 9.6 us, 1,024: 8.8 vs
 // 10.3; profiles/r06_ab_persist_small_batches.txt).
@@ -786,11 +593,8 @@ bool plan_bwd(int64_t n, int L, int C, bool sharedF, int cus, BwdPlan& b) {
   static const int kEnvNseg = LV_KNOB("LV_BWD_NSEG", 0);      // A/B testing only
   static const int kEnvGlobal = LV_KNOB("LV_BWD_FGLOBAL", 0);  // force the fallback (tests)
   static const int kEnvPersistMin = LV_KNOB("LV_BWD_PERSIST_MIN", -1);  // A/B; 0 = off, -1 = 3 * CUs + 1
-  static const int kEnvVariantP = LV_KNOB("LV_BWD_VARIANT", kBwdVariantDefault);
-  const bool single = (kEnvVariantP & kBwdVarPersistSingle) != 0;  // A/B: one tile buffer
   static const int kEnvPersistBpc = LV_KNOB("LV_BWD_PERSIST_BPC", 0);  // A/B: blocks per CU (grid)
-  const int64_t persist_blocks =
-      (int64_t)cus * (kEnvPersistBpc > 0 ? kEnvPersistBpc : single ? kBwdPersistBlocksPerCU : kBwdPersistBlocksPerCUDB);
+  const int64_t persist_blocks = (int64_t)cus * (kEnvPersistBpc > 0 ? kEnvPersistBpc : kBwdPersistBlocksPerCU);
   const int64_t persist_min = kEnvPersistMin < 0 ? (int64_t)cus + 1 : kEnvPersistMin;
   b = BwdPlan{};
   const int64_t MC = (int64_t)(L + 1) * (L + 1) * C;
@@ -807,8 +611,7 @@ bool plan_bwd(int64_t n, int L, int C, bool sharedF, int cus, BwdPlan& b) {
       b.gx = (int)std::min<int64_t>(groups, persist_blocks);
       plan_segments(L, b.nseg, kTilePrologue, true, b.seg_lo);
       if (!env_masks("LV_BWD_MASKS", L, b.nseg, b.seg_mask)) balance_masks(L, b.nseg, true, b.seg_mask);
-      const bool pad = single && (kEnvVariantP & kBwdVarPersistPad) != 0;
-      b.lds = sizeof(float) * (size_t)persist_lds_floats(L, b.nseg, single ? 1 : 2, pad);
+      b.lds = sizeof(float) * (size_t)persist_lds_floats(L, b.nseg);
       const size_t slabs = sizeof(float) * (size_t)b.gx * (size_t)(slab_chunks(MC) * kSlabChunk);
       b.ws_gang_off = slabs;
       b.ws = slabs + sizeof(float) * 3 * (size_t)std::max<int64_t>(n, 1);
@@ -845,6 +648,7 @@ bool plan_bwd(int64_t n, int L, int C, bool sharedF, int cus, BwdPlan& b) {
         for (int k = 0; k < nseg; ++k) fp = std::max(fp, fseg_rows(b.seg_lo[k], b.seg_lo[k + 1]) * C);
       b.fpitch = (fp + 3) & ~3;
       const size_t fregion = ct ? (size_t)((MC + 3) & ~3) : (size_t)nseg * b.fpitch;
+      // 12 * Sw (the retired VJP tail's v / mu) stays: without it a larger Sw fits at some (l, C) -- another sum order
       const size_t lds = (size_t)tile_stage_bytes(Sw, MC, 4) +
                          sizeof(float) * ((size_t)bwd_trig_floats(Sw, L) + (size_t)nseg * 64 * 3 +
                                           (fmode == kBwdFShared ? (size_t)MC : 0) +
@@ -904,6 +708,7 @@ int action_bwd_common(const float* ang, const float* F, int64_t F_batch_stride,
   }
   LV_CHECK_ARG(ang && F && gout && gF && (gang || v), "null pointer argument");
   LV_CHECK_ARG(!v || (gv && (!mu || gmu)), "null VJP output");
+  LV_CHECK_ARG(!v || sharedF, "the fused backward takes a shared spectrum");
   BwdPlan b;
   LV_CHECK_ARG(plan_bwd_cached(n, L, C, sharedF, b), "no backward plan fits the LDS budget (l=%d, C=%d)", L, C);
   if (sharedF && (ws_bytes < b.ws || !workspace)) {
@@ -915,11 +720,9 @@ int action_bwd_common(const float* ang, const float* F, int64_t F_batch_stride,
   p.a.F = F;
   p.a.Fstride = F_batch_stride;
   p.a.gout = gout;
-  p.a.gang = gang;
-  p.a.v = v;
-  p.a.mu = mu;
-  p.a.gv = gv;
-  p.a.gmu = gmu;
+  // fused path: the kernel writes the angle gradient to the workspace and the exp -> ZYZ VJP
+  // runs in the reduce's launch, beside it
+  p.a.gang = v ? reinterpret_cast<float*>(static_cast<char*>(workspace) + b.ws_gang_off) : gang;
   p.a.gF = gF;
   p.a.ws_F = (float*)workspace;
   p.a.n = n;
@@ -929,15 +732,6 @@ int action_bwd_common(const float* ang, const float* F, int64_t F_batch_stride,
   p.a.Sw = b.Sw;
   p.a.transpose = transpose ? 1 : 0;
   p.a.fpitch = b.fpitch;
-  static const int kEnvBwdPrio = LV_KNOB("LV_BWD_PRIO", 0);  // A/B: 2 = prologue-priority phases
-  p.a.prio = kEnvBwdPrio;
-  // dF slab reduce: LV_BWD_REDUCE (A/B) 6 = chunk-major slabs + action_bwd_reduce5_kernel
-  // (default), 3 / 5 = the same slabs + reduce3 / reduce4, 16 / 8 / 4 = row slabs +
-  // action_bwd_reduce2_kernel<COLS>, 1 = the round-2 kernel
-  static const int kEnvReduce = LV_KNOB("LV_BWD_REDUCE", kBwdReduceDefault);
-  p.a.slab_chunked = b.fmode != kBwdFSample && (kEnvReduce == 3 || kEnvReduce == 5 || kEnvReduce == 6);
-  static const int kEnvVariant = LV_KNOB("LV_BWD_VARIANT", kBwdVariantDefault);
-  p.a.variant = kEnvVariant;
   p.a.stamps = ab_stamps();
   for (int k = 0; k <= b.nseg; ++k) p.a.seg_lo[k] = b.seg_lo[k];
   for (int k = 0; k < kMaxSeg; ++k) p.a.seg_mask[k] = b.seg_mask[k];
@@ -947,89 +741,18 @@ int action_bwd_common(const float* ang, const float* F, int64_t F_batch_stride,
   p.lds = b.lds;
   p.stream = st;
   p.persist = b.persist;
-  if (b.persist) {
-    // the persistent kernel writes the angle gradient (the fused path: into the workspace,
-    // then the per-sample exp -> ZYZ VJP below) and chunk-major slabs, one per block
-    p.a.slab_chunked = 1;
-    if (v) p.a.gang = reinterpret_cast<float*>(static_cast<char*>(workspace) + b.ws_gang_off);
-    p.a.v = nullptr;
-    p.a.mu = nullptr;
-    if (int e = kBwdRun[L](p)) return e;
-    static const int kEnvReduceP = LV_KNOB("LV_BWD_REDUCE", kBwdReduceDefault);
-    static const int kEnvVjpMerge = LV_KNOB("LV_BWD_VJP_MERGE", 1);  // A/B: 0 = separate VJP launch
-    if (kEnvReduceP == 6 && v && kEnvVjpMerge) {
-      // fused path: the VJP blocks and the dF reduce in one launch (side by side)
-      const int nvjp = (int)((n + 255) / 256);
-      hipLaunchKernelGGL(action_bwd_reduce5_vjp_kernel, dim3((unsigned)(nvjp + slab_chunks(MC))), dim3(256), 0,
-                         st, (const float*)workspace, gF, MC, b.gx, nvjp, mu, v, (const float*)p.a.gang, gmu,
-                         gv, n);
-      LV_RETURN_LAUNCH("action_bwd_reduce5_vjp_kernel");
-    }
-    if (kEnvReduceP == 6)
-      hipLaunchKernelGGL(action_bwd_reduce5_kernel, dim3((unsigned)slab_chunks(MC)), dim3(256), 0, st,
-                         (const float*)workspace, gF, MC, b.gx);
-    else
-      hipLaunchKernelGGL(action_bwd_reduce3_kernel, dim3((unsigned)slab_chunks(MC)), dim3(1024), 0, st,
-                         (const float*)workspace, gF, MC, b.gx, p.a.stamps);
-    LV_CHECK_LAUNCH("action_bwd_reduce_kernel");
-    if (v) return lv_exp_eazyz_vjp(mu, v, p.a.gang, gmu, gv, n, st);
-    return LV_OK;
-  }
-  // fused path: the tile kernel writes the angle gradient to the workspace and the
-  // exp -> ZYZ VJP runs in the reduce's launch, beside it, instead of on wave 0 of every
-  // block after its chain (A/B LV_BWD_TAIL_VJP = 1): 4,096 samples 17.2 -> 15.3 us per
-  // fused backward, 512: 10.9 -> 9.9 (profiles/r05_tail_vjp_ab.txt)
-  static const int kEnvTailVjp = LV_KNOB("LV_BWD_TAIL_VJP", 0);
-  const bool vjp_beside = v && sharedF && p.a.slab_chunked && kEnvReduce == 6 && !kEnvTailVjp;
-  if (vjp_beside) {
-    p.a.gang = reinterpret_cast<float*>(static_cast<char*>(workspace) + b.ws_gang_off);
-    p.a.v = nullptr;
-    p.a.mu = nullptr;
-  }
   if (int e = kBwdRun[L](p)) return e;
   if (!sharedF) return LV_OK;
-  if (vjp_beside) {
+  // dF slab reduce (reduce5_chunk), with the VJP blocks beside it on the fused path
+  if (v) {
     const int nvjp = (int)((n + 255) / 256);
     hipLaunchKernelGGL(action_bwd_reduce5_vjp_kernel, dim3((unsigned)(nvjp + slab_chunks(MC))), dim3(256), 0, st,
                        (const float*)workspace, gF, MC, b.gx, nvjp, mu, v, (const float*)p.a.gang, gmu, gv, n);
     LV_RETURN_LAUNCH("action_bwd_reduce5_vjp_kernel");
   }
-  // dF slab reduce: chunk-major slabs + action_bwd_reduce5_kernel by default (kBwdReduceDefault;
-  // reduce3 before it, profiles/r04_bwd_reduce_ab.txt: 16.0 vs 18.0 us per lv_group_action_bwd call at batch
-  // 4,096, 187 vs 191 at 65,536, 9.9 vs 9.8 at 512 against reduce2<16>, the round-3
-  // default; an in-kernel reduction by the tile kernel's last blocks -- completion counter,
-  // device-scope release fences -- ran 75 us per call at 4,096 and was dropped)
-  if (p.a.slab_chunked && kEnvReduce == 6) {
-    hipLaunchKernelGGL(action_bwd_reduce5_kernel, dim3((unsigned)slab_chunks(MC)), dim3(256), 0, st,
-                       (const float*)workspace, gF, MC, b.gx);
-    LV_RETURN_LAUNCH("action_bwd_reduce5_kernel");
-  }
-  if (p.a.slab_chunked && kEnvReduce == 5) {
-    hipLaunchKernelGGL(action_bwd_reduce4_kernel, dim3((unsigned)slab_chunks(MC)), dim3(1024), 0, st,
-                       (const float*)workspace, gF, MC, b.gx);
-    LV_RETURN_LAUNCH("action_bwd_reduce4_kernel");
-  }
-  if (p.a.slab_chunked) {
-    hipLaunchKernelGGL(action_bwd_reduce3_kernel, dim3((unsigned)slab_chunks(MC)), dim3(1024), 0, st,
-                       (const float*)workspace, gF, MC, b.gx, p.a.stamps);
-    LV_RETURN_LAUNCH("action_bwd_reduce3_kernel");
-  }
-  if (kEnvReduce == 8) {
-    hipLaunchKernelGGL(action_bwd_reduce2_kernel<8>, dim3(ceil_div(MC, 8)), dim3(1024), 0, st,
-                       (const float*)workspace, gF, MC, b.gx);
-    LV_RETURN_LAUNCH("action_bwd_reduce2_kernel");
-  } else if (kEnvReduce == 16) {
-    hipLaunchKernelGGL(action_bwd_reduce2_kernel<16>, dim3(ceil_div(MC, 16)), dim3(1024), 0, st,
-                       (const float*)workspace, gF, MC, b.gx);
-    LV_RETURN_LAUNCH("action_bwd_reduce2_kernel");
-  } else if (kEnvReduce == 4) {
-    hipLaunchKernelGGL(action_bwd_reduce2_kernel<4>, dim3(ceil_div(MC, 4)), dim3(1024), 0, st,
-                       (const float*)workspace, gF, MC, b.gx);
-    LV_RETURN_LAUNCH("action_bwd_reduce2_kernel");
-  }
-  hipLaunchKernelGGL(action_bwd_reduce_kernel, dim3(ceil_div(MC, kBwdReduceCols)), dim3(64 * kBwdReduceWaves),
-                     0, st, (const float*)workspace, gF, MC, b.gx);
-  LV_RETURN_LAUNCH("action_bwd_reduce_kernel");
+  hipLaunchKernelGGL(action_bwd_reduce5_kernel, dim3((unsigned)slab_chunks(MC)), dim3(256), 0, st,
+                     (const float*)workspace, gF, MC, b.gx);
+  LV_RETURN_LAUNCH("action_bwd_reduce5_kernel");
 }
 }  // namespace
 

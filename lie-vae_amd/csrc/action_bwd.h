@@ -23,52 +23,34 @@ namespace lv {
 // spectrum -> the tile leaves as gF with one contiguous flush; shared spectrum -> each
 // wave sums its rows over the group's samples (fixed order) into the block's LDS slab;
 // blocks loop over groups (grid capped so the workspace stays
-// bounded), write their slab to the workspace once, and action_bwd_reduce_kernel sums
-// the slabs in block order.  No atomics: bitwise reproducible.
+// bounded), write their slab to the workspace once, and action_bwd_reduce5_kernel sums
+// the slabs in a fixed order.  No atomics: bitwise reproducible.
 // FM (spectrum mode): kBwdFSample per-sample spectrum, kBwdFShared shared spectrum with
 // its slices and the dF slab in LDS, kBwdFSharedGlobal shared spectrum read from global
 // memory and the slab accumulated in place in the block's workspace row -- the fallback
 // for tiles too large to leave room for both (large C at high l); same summation order,
 // so bitwise equal to kBwdFShared for the same plan.
 constexpr int kBwdFSample = 0, kBwdFShared = 1, kBwdFSharedGlobal = 2;
-constexpr int kBwdVarJit = 1;  // ActionBwdArgs::variant: row-pair reads of F and G (wide kernel)
-// one-group blocks' post-chain slab pass (A/B): flat element list over the wave's degrees
-// (else one pass set per degree), and write-through (sc1) slab stores (else plain)
-constexpr int kBwdVarSlabFlat = 2, kBwdVarSlabWT = 4;
-// one-group compile-time-C blocks: the barrier after the prologue split in two, so each
-// wave's first (largest) degree computes its forward recompute P1..P4 -- which needs the
-// multiples and the spectrum, not the gradient tile -- while the tile's LDS-DMA is in flight
-constexpr int kBwdVarSplit = 8;
-// prologue tasks spread over the block's waves (see action_bwd_tile_kernel)
-constexpr int kBwdVarSpread = 16;
 struct ActionBwdArgs {
   const float* ang;
   const float* F;
   int64_t Fstride;
   const float* gout;
-  float* gang;         // may be null when v is set (fused: the angle gradient stays in LDS)
-  const float* v;      // fused exp -> ZYZ VJP in the tail (lv_fused_exp_action_bwd), or null
-  const float* mu;     // (n,3,3) or null
-  float* gv;
-  float* gmu;
+  float* gang;         // the caller's, or a workspace region (fused: the host runs the VJP after)
   float* gF;           // per-sample spectrum: written directly
-  float* ws_F;         // [gridDim.x][M*C] (shared F only)
+  float* ws_F;         // dF slabs, chunk-major: [slab_chunks(M*C)][gridDim.x][16] (shared F only)
   int64_t n;
   int64_t MC;
   int64_t groups;      // ceil(n / Sw); block b takes groups b, b + gridDim.x, ...
   int C, Sw, transpose;
   int fpitch;          // floats per wave-private spectrum slice in LDS
-  int prio;            // 2: group load + prologue at s_setprio 3, chain at 0 (A/B: 0 off)
-  int slab_chunked;    // kBwdFShared slab layout: 0 [block][M*C], 1 [M*C/16][block][16]
-  int variant;         // kernel variant bits (kBwdVar*)
   unsigned long long* stamps;  // phase timestamps (A/B timeline tool; null in the product)
   int seg_lo[kMaxSeg + 1];      // contiguous degree ranges (run-time-C kernel, LDS spectrum)
   unsigned seg_mask[kMaxSeg];   // degree set of wave k (bit l = degree l)
 };
 
-// Chunk-major dF slabs (slab_chunked): element e of block b at
-// ((e / 16) * gridDim.x + b) * 16 + e % 16, so that the reduce reads each 16-element chunk's
-// slabs as one contiguous run (action_bwd_reduce3_kernel).
+// Chunk-major dF slabs: element e of block b at ((e / 16) * gridDim.x + b) * 16 + e % 16, so
+// that the reduce reads each 16-element chunk's slabs as one contiguous run (reduce5_chunk).
 constexpr int kSlabChunk = 16;
 __host__ __device__ inline int64_t slab_chunks(int64_t MC) { return (MC + kSlabChunk - 1) / kSlabChunk; }
 
@@ -183,20 +165,14 @@ __host__ __device__ constexpr bool bwd_wide(int L, int C, int fmode, int64_t gro
   return L <= kBwdWideMaxL && C == kTileFastC && fmode == kBwdFShared && gx >= groups;
 }
 
-// This block's dF slab elements [g0, g0 + cnt) (a wave's rows) from LDS to the workspace,
-// row layout ([block][M*C]) or chunk-major (slab_chunked).
+// This block's dF slab elements [g0, g0 + cnt) (a wave's rows) from LDS to the workspace.
 __device__ __forceinline__ void write_slab_rows(const ActionBwdArgs& a, const float* slabL, int g0, int cnt,
                                                 int lane) {
-  if (a.slab_chunked) {
-    float* ws = a.ws_F + (int64_t)blockIdx.x * kSlabChunk;
-    const int64_t cstride = (int64_t)gridDim.x * kSlabChunk;
-    for (int e = lane; e < cnt; e += 64) {
-      const int g = g0 + e;
-      ws[(g / kSlabChunk) * cstride + g % kSlabChunk] = slabL[g];
-    }
-  } else {
-    float* slab = a.ws_F + (int64_t)blockIdx.x * a.MC;
-    for (int e = lane; e < cnt; e += 64) slab[g0 + e] = slabL[g0 + e];
+  float* ws = a.ws_F + (int64_t)blockIdx.x * kSlabChunk;
+  const int64_t cstride = (int64_t)gridDim.x * kSlabChunk;
+  for (int e = lane; e < cnt; e += 64) {
+    const int g = g0 + e;
+    ws[(g / kSlabChunk) * cstride + g % kSlabChunk] = slabL[g];
   }
 }
 
@@ -206,12 +182,12 @@ __device__ __forceinline__ void write_slab_rows(const ActionBwdArgs& a, const fl
 // spills at l = 10 vs 220 VGPRs and none; 31.4 -> 28.0 us per call at batch 4096,
 // profiles/r02_bwd_regbudget_sweep.txt), so the launcher uses it whenever the grid covers
 // the batch.
-// WPE: waves per SIMD the register budget is sized for (3 only for the bwd_wide case).
-// JIT: the spectrum column and G read in row pairs inside the products (A/B variant bit
-// kBwdVarJit of ActionBwdArgs::variant; wide kernel only).
-template <int LT, int CT, int FM, bool LOOP = true, int WPE = 2, bool JIT = false>
+// WPE: waves per SIMD the register budget is sized for (3 only for the bwd_wide case, which
+// also reads the spectrum column and G in row pairs inside the products: the JIT chain).
+template <int LT, int CT, int FM, bool LOOP = true, int WPE = 2>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE)))
 void action_bwd_tile_kernel(ActionBwdArgs a) {
+  constexpr bool JIT = WPE == 3;
   constexpr bool SHAREDF = FM != kBwdFSample;
   constexpr bool GSLAB = FM == kBwdFSharedGlobal;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -236,22 +212,18 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
   const int stage_bytes = tile_stage_bytes(Sw, MC, 4);
   // LDS: [gout / dF tile][multiples table][angle partials][dF slab (shared F)][spectrum:
   //      CT > 0 the whole (M, C) row-major, else per-wave column-major slices]
-  //      [fused path: the group's v (and mu), Sw * 12 floats]
   float* trig = lds + (stage_bytes >> 2);
   float* apart = trig + bwd_trig_floats(Sw, LT);               // [nseg][64][3]
-  // dF slab: LDS [M*C] (kBwdFShared), or this block's workspace row (kBwdFSharedGlobal)
-  float* slabL = GSLAB ? a.ws_F + (int64_t)blockIdx.x * MC : apart + (nthr >> 6) * 64 * 3;
-  // slab element g: LDS (kBwdFShared), or this block's workspace slab in the row or the
-  // chunk-major layout (kBwdFSharedGlobal; the layout the reduce kernel reads)
+  float* slabL = apart + (nthr >> 6) * 64 * 3;  // dF slab in LDS [M*C] (kBwdFShared)
+  // slab element g: LDS (kBwdFShared), or this block's chunk-major workspace slab
+  // (kBwdFSharedGlobal; the layout the reduce kernel reads)
   auto slab_at = [&](int g) -> float& {
-    if constexpr (GSLAB) {
-      if (a.slab_chunked)
-        return a.ws_F[((int64_t)(g / kSlabChunk) * gridDim.x + blockIdx.x) * kSlabChunk + g % kSlabChunk];
-    }
-    return slabL[g];
+    if constexpr (GSLAB)
+      return a.ws_F[((int64_t)(g / kSlabChunk) * gridDim.x + blockIdx.x) * kSlabChunk + g % kSlabChunk];
+    else
+      return slabL[g];
   };
-  float* const Fbase = apart + (nthr >> 6) * 64 * 3 + (FM == kBwdFShared ? (int)MC : 0);
-  const int fsize = CT > 0 ? (((int)MC + 3) & ~3) : (nthr >> 6) * a.fpitch;
+  float* const Fbase = slabL + (FM == kBwdFShared ? (int)MC : 0);
   float* Fw = Fbase + (CT > 0 ? 0 : wave * a.fpitch);
   // spectrum (shared F): once per block -- CT > 0: element e = tid + k * nthr of the whole
   // (M, C) by every thread, loads issued together; else this wave's column-major slice
@@ -264,26 +236,17 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
   // Degrees walked largest first (every instantiation, so that all spectrum modes and the
   // looping kernel add a sample's angle-gradient partials in the same order); kDesc: the
   // one-group compile-time-C kernel also loads its prologue inputs ahead of the tile DMA
-  // and may split the prologue barrier (kBwdVarSplit: the largest degree's forward
-  // recompute overlapping the tile DMA)
   constexpr bool kDesc = CT > 0 && !LOOP && FM == kBwdFShared;
-  // kBwdVarSpread: task t on lane t / nw of wave t % nw (the prologue's serial chains on
-  // every SIMD), else thread t (all tasks in wave 0); the host guarantees 3*Sw <= blockDim.x
-  const int t_task = (a.variant & kBwdVarSpread) ? lane * (nthr >> 6) + wave : tid;
-  const bool task = t_task < 3 * Sw;
-  const int jt = t_task / 3, q = t_task - 3 * (t_task / 3);
-  // kDesc: the prologue's angle and the VJP tail's v / mu loaded before the spectrum, so
-  // the spectrum staging's wait covers them and nothing after the tile DMA waits in vmcnt
-  // order behind it
-  float ang0 = 0.f, vmu0 = 0.f;
+  // prologue task t = (sample, slot) on thread t; the host guarantees 3*Sw <= blockDim.x
+  const bool task = tid < 3 * Sw;
+  const int jt = tid / 3, q = tid - 3 * (tid / 3);
+  // kDesc: the prologue's angle loaded before the spectrum, so the spectrum staging's wait
+  // covers it and nothing after the tile DMA waits in vmcnt order behind it
+  float ang0 = 0.f;
   if constexpr (kDesc) {
     const int64_t s0e = (int64_t)blockIdx.x * Sw;
     const int Sve = (int)min((int64_t)Sw, a.n - s0e);
     if (task) ang0 = a.ang[(s0e + min(jt, Sve - 1)) * 3 + (a.transpose ? 2 - q : q)];
-    if (a.v && tid < 12 * Sve && 12 * Sve <= nthr) {  // else the loop after the DMA
-      const int js = tid / 12, k = tid - 12 * js;
-      vmu0 = k < 3 ? a.v[(s0e + js) * 3 + k] : (a.mu ? a.mu[(s0e + js) * 9 + (k - 3)] : 0.f);
-    }
   }
   if constexpr (GSLAB) {
     each_degree([&](int l) {  // this wave's rows
@@ -329,9 +292,6 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
       }
     }
   }
-  // fused path: the exp -> ZYZ VJP's inputs, loaded by the prologue threads so that the
-  // tail does not wait on global loads (after the spectrum)
-  float* vmu = Fbase + fsize;
   const float* Fl = GSLAB ? a.F + c : (CT > 0 ? Fw + c : Fw + c * frows - rows_lo);
   const int fstep = (GSLAB || CT > 0) ? C : 1;
 
@@ -341,7 +301,6 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
     const int Sv = (int)min((int64_t)Sw, a.n - s0);
     const bool active = j < Sv;
     const int nbytes = Sv * (int)MC * 4;
-    if (a.prio >= 2) __builtin_amdgcn_s_setprio(3);
     // 1. upstream-gradient tile: global -> LDS by LDS-DMA (global_load_lds, 16-byte body,
     //    4-byte head/tail), issued first thing.  No VGPR holds the tile in flight: the
     //    register-staged form kept 32 VGPRs of loads live across the prologue, which the
@@ -375,25 +334,11 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
       if (a.transpose) sq = -sq;
       trig_row_fill1<LT>(trig + jt * kRow, cq, sq, q, LT);
     }
-    if (kDesc && a.v && 12 * Sv <= nthr) {
-      if (tid < 12 * Sv) vmu[tid] = vmu0;
-    } else if (a.v) {  // v (3) and mu (9) of the group's samples for the VJP tail (12 * Sv
-                       // may exceed the block: 252 values at C = 3)
-      for (int t = tid; t < 12 * Sv; t += nthr) {
-        const int js = t / 12, k = t - 12 * js;
-        if (k < 3) vmu[js * 12 + k] = a.v[(s0 + js) * 3 + k];
-        else if (a.mu) vmu[js * 12 + k] = a.mu[(s0 + js) * 9 + (k - 3)];
-      }
-    }
-    // 3. the LDS-DMA writes of this wave have landed (an LDS-DMA is counted in vmcnt);
-    //    kBwdVarSplit: only the multiples, the spectrum and v / mu here (LDS writes), the
-    //    tile after the first degree's forward recompute
-    bool split_pending = kDesc && (a.variant & kBwdVarSplit) != 0;
-    if (!split_pending) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // 3. the LDS-DMA writes of this wave have landed (an LDS-DMA is counted in vmcnt)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     block_sync_lds();
     phase_stamp(a.stamps, wave, 1);
 
-    if (a.prio >= 2) __builtin_amdgcn_s_setprio(0);
     float* tile_lane = reinterpret_cast<float*>(stage_b) + j * MC + c;
     const float* tj = trig + min(j, Sw - 1) * kRow;
     const float* Fs = a.F + (s0 + min(j, Sv - 1)) * a.Fstride + c;  // per-sample spectrum
@@ -421,11 +366,10 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
         jmul<l>(u, p2);                           // P2
         xm<l>(mult_lds<l, 1, LT>(tj), p2, u);     // P3
         jmul<l>(u, p4);                           // P4
-        if (split_pending) {  // the wave's first degree: now the tile
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          block_sync_lds();
-          split_pending = false;
-        }
+        // scheduling fence (no instruction): the G column's LDS reads stay below the forward
+        // recompute.  Hoisted over it they cost the one-group builds registers: 156 instead of
+        // 95 VGPRs at l = 10, 77 spilled VGPRs at l = 20.
+        if constexpr (kDesc) __builtin_amdgcn_sched_barrier(0);
         if constexpr (JIT) {
           xm_mem<l, true>(mult_lds<l, 0, LT>(tj), tile_lane + r0 * C, C, u);  // Q4
         } else {
@@ -476,10 +420,6 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
         if (a.stamps) degree_stamp(a.stamps, wave, l);
       }
     });
-    if (split_pending) {  // a wave without degrees still takes the tile barrier
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      block_sync_lds();
-    }
     phase_stamp(a.stamps, wave, 2);
     if constexpr (FM == kBwdFShared && !LOOP) {
       // one group per block: this wave's rows of the slab are the group's dF rows summed
@@ -491,17 +431,9 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
       const float* t0 = reinterpret_cast<const float*>(stage_b);
       constexpr int kSw = CT > 0 ? 64 / CT : 1;
       const bool full = CT > 0 && Sv == kSw && Sw == kSw;
-      // write-through (sc1, kBwdVarSlabWT) or plain slab stores
-      const int64_t slab_floats = (int64_t)gridDim.x * (a.slab_chunked ? slab_chunks(MC) * kSlabChunk : MC);
-      const __amdgpu_buffer_rsrc_t wrs =
-          __builtin_amdgcn_make_buffer_rsrc(a.ws_F, 0, (int)(slab_floats * 4), kRawBufferFlags);
       const int64_t cstride = (int64_t)gridDim.x * kSlabChunk;
-      const bool wt = (a.variant & kBwdVarSlabWT) != 0;
       auto put = [&](int g, float sum) {
-        const int64_t idx = a.slab_chunked ? (g / kSlabChunk) * cstride + (int64_t)blockIdx.x * kSlabChunk + g % kSlabChunk
-                                           : (int64_t)blockIdx.x * MC + g;
-        if (wt) tile_store_elem<16>(wrs, (int)(idx * 4), sum);
-        else a.ws_F[idx] = sum;
+        a.ws_F[(g / kSlabChunk) * cstride + (int64_t)blockIdx.x * kSlabChunk + g % kSlabChunk] = sum;
       };
       // a range [g0, g0 + cnt) of slab elements, kU per lane per pass with all their LDS
       // loads issued before any sum or store; idx maps a range position to the element
@@ -534,22 +466,7 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
           }
         }
       };
-      if (a.variant & kBwdVarSlabFlat) {
-        // the wave's elements as one flat list over its degrees (ascending)
-        int tot = 0;
-        each_degree([&](int l) { tot += (2 * l + 1) * C; });
-        sum_range(tot, [&](int e) {
-          int off = 0, g = 0;
-          each_degree([&](int l) {
-            const int cnt = (2 * l + 1) * C;
-            if (e >= off && e < off + cnt) g = l * l * C + (e - off);
-            off += cnt;
-          });
-          return g;
-        });
-      } else {
-        each_degree([&](int l) { sum_range((2 * l + 1) * C, [&](int e) { return l * l * C + e; }); });
-      }
+      each_degree([&](int l) { sum_range((2 * l + 1) * C, [&](int e) { return l * l * C + e; }); });
     }
     phase_stamp(a.stamps, wave, 3);
     // angle gradients: sum over the C lanes of a sample (column order), then segments
@@ -570,40 +487,14 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
         for (int cc2 = 0; cc2 < C; ++cc2) sw += apart[(w * 64 + js * C + cc2) * 3 + i];
         r += sw;
       }
-      if (a.gang) a.gang[(s0 + js) * 3 + i] = r;
-      if (a.v) trig[js * 3 + i] = r;  // the chains are done: the table is free
+      a.gang[(s0 + js) * 3 + i] = r;
     }
-    if (!LOOP && SHAREDF && wave > 0) {  // the tail below is wave 0's (tid < 3 * Sw)
-      phase_stamp(a.stamps, wave, 5);
-      return;
-    }
-    if (a.v) {  // fused path: exp -> ZYZ VJP of the group's samples (exp_eazyz_vjp_sample)
-      if constexpr (!LOOP && SHAREDF) wave_lds_sync();  // wave 0 alone from here
-      else block_sync_lds();
-      if (tid < Sv) {
-        const int64_t s = s0 + tid;
-        float av[3], g[3], m[9], gm[9], o[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { av[k] = vmu[tid * 12 + k]; g[k] = trig[tid * 3 + k]; }
-        if (a.mu) {
-#pragma unroll
-          for (int k = 0; k < 9; ++k) m[k] = vmu[tid * 12 + 3 + k];
-        }
-        exp_eazyz_vjp_sample(av, a.mu != nullptr, m, g, gm, o);
-        if (a.mu) {
-#pragma unroll
-          for (int k = 0; k < 9; ++k) a.gmu[s * 9 + k] = gm[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) a.gv[s * 3 + k] = o[k];
-      }
-    }
-    if constexpr (!SHAREDF)
-      tile_flush<float, 1>(a.gF + s0 * MC, stage_b, mis, nbytes, tid, nthr);
     if constexpr (!LOOP && SHAREDF) {
       phase_stamp(a.stamps, wave, 5);
       return;
     }
+    if constexpr (!SHAREDF)
+      tile_flush<float, 1>(a.gF + s0 * MC, stage_b, mis, nbytes, tid, nthr);
     block_sync_lds();  // the next group overwrites the tile, the table and the partials
   }
   if constexpr (FM == kBwdFShared)
@@ -613,9 +504,6 @@ void action_bwd_tile_kernel(ActionBwdArgs a) {
 }  // namespace lv
 #include "action_bwd_persist.h"
 namespace lv {
-
-// Slab count per block of action_bwd_reduce_kernel (defined in action.hip).
-constexpr int kBwdReduceWaves = 16;
 
 struct BwdLaunch {
   ActionBwdArgs a;
@@ -629,55 +517,29 @@ template <int LT>
 struct BwdLauncher {
   static int run(BwdLaunch& p);  // out of class: see FwdLauncher
 };
+// Only the kernels the planner (plan_bwd in action.hip) can choose at this l_max are compiled.
 template <int LT>
 int BwdLauncher<LT>::run(BwdLaunch& p) {
   const dim3 grid(p.gx), block(64 * p.nseg);
   if (p.persist) {
-    if constexpr (LT <= kBwdPersistMaxL) {
-      const bool single = (p.a.variant & kBwdVarPersistSingle) != 0;
-      const int pv = ((p.a.variant & kBwdVarPersistPad) ? 1 : 0) | ((p.a.variant & kBwdVarPersistAng) ? 2 : 0) |
-                     ((p.a.variant & kBwdVarPersistBufDma) ? 4 : 0) | ((p.a.variant & kBwdVarPersistLaneMap) ? 8 : 0) |
-                     ((p.a.variant & kBwdVarPersistSlabWT) ? 16 : 0);
-      // built single-buffer variants: 0 (round 5), 2 (LDS angle sums), 3 (+ padded tile),
-      // 6 (+ buffer DMA), 7 (padded tile by buffer DMA), 14 (+ lane map), 22 (6 + write-through
-      // slab stores); the A/B library refuses other combinations
-      if (single && pv == 22)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 22>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 7)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 7>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 14)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 14>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 6)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 6>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 3)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 3>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 2)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true, 3, 2>), grid, block, p.lds, p.stream, p.a);
-      else if (single && pv == 0)
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves, false, true>), grid, block, p.lds, p.stream, p.a);
-      else if (single) {
-        set_error("persistent backward variant %d not built", pv);
-        return LV_ERR_ARG;
-      }
-      else
-        hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves>), grid, block, p.lds, p.stream, p.a);
+    if constexpr (LT >= kBwdPersistWaves - 1 && LT <= kBwdPersistMaxL) {
+      hipLaunchKernelGGL((action_bwd_persist_kernel<LT, kBwdPersistWaves>), grid, block, p.lds, p.stream, p.a);
+      LV_RETURN_LAUNCH("action_bwd_persist_kernel");
+    } else {
+      set_error("no persistent backward kernel at l_max = %d", LT);
+      return LV_ERR_ARG;
     }
-    LV_RETURN_LAUNCH("action_bwd_persist_kernel");
   }
   if (p.fmode == kBwdFSample)
     hipLaunchKernelGGL((action_bwd_tile_kernel<LT, 0, kBwdFSample>), grid, block, p.lds, p.stream, p.a);
   else if (p.fmode == kBwdFSharedGlobal)
     hipLaunchKernelGGL((action_bwd_tile_kernel<LT, 0, kBwdFSharedGlobal>), grid, block, p.lds, p.stream, p.a);
-  else if (bwd_wide(LT, p.a.C, p.fmode, p.a.groups, p.gx)) {
-    if constexpr (LT <= kBwdWideMaxL) {
-      if (p.a.variant & kBwdVarJit)
-        hipLaunchKernelGGL((action_bwd_tile_kernel<LT, kTileFastC, kBwdFShared, false, 3, true>), grid, block, p.lds, p.stream, p.a);
-      else
-        hipLaunchKernelGGL((action_bwd_tile_kernel<LT, kTileFastC, kBwdFShared, false, 3>), grid, block, p.lds, p.stream, p.a);
-    }
-  } else if (p.a.C == kTileFastC && p.gx >= p.a.groups)
-    hipLaunchKernelGGL((action_bwd_tile_kernel<LT, kTileFastC, kBwdFShared, false>), grid, block, p.lds, p.stream, p.a);
-  else if (p.a.C == kTileFastC)
+  else if (p.a.C == kTileFastC && p.gx >= p.a.groups) {
+    // one group per block: bwd_wide (3 waves per SIMD, JIT chain) up to kBwdWideMaxL
+    constexpr int kWpe = LT <= kBwdWideMaxL ? 3 : 2;
+    static_assert(bwd_wide(LT, kTileFastC, kBwdFShared, 1, 1) == (kWpe == 3), "bwd_wide");
+    hipLaunchKernelGGL((action_bwd_tile_kernel<LT, kTileFastC, kBwdFShared, false, kWpe>), grid, block, p.lds, p.stream, p.a);
+  } else if (p.a.C == kTileFastC)
     hipLaunchKernelGGL((action_bwd_tile_kernel<LT, kTileFastC, kBwdFShared>), grid, block, p.lds, p.stream, p.a);
   else
     hipLaunchKernelGGL((action_bwd_tile_kernel<LT, 0, kBwdFShared>), grid, block, p.lds, p.stream, p.a);

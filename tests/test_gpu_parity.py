@@ -698,6 +698,66 @@ def test_action_bwd_global_spectrum_mode_bitwise(gpu_device, tmp_path):
     assert np.array_equal(outs[0]["gf"], outs[1]["gf"])
 
 
+_BWD_AB_SCRIPT = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+import lie_vae._lib as lib
+from lie_vae._lib import call, ptr, stream
+dev = torch.device("cuda:0")
+L, C = 10, 10
+M = (L + 1) ** 2
+out = {}
+for tag, n, transpose in (("one", 777, 1), ("persist", 6 * (lib.load().lv_compute_units() + 1) + 5, 0)):
+    g = torch.Generator().manual_seed(n)
+    ang = (torch.rand(n, 3, generator=g) * 6 - 3).to(dev)
+    v = torch.randn(n, 3, generator=g).to(dev)
+    F = torch.randn(M, C, generator=g).to(dev)
+    gout = torch.randn(n, M, C, generator=g).to(dev)
+    q = torch.linalg.qr(torch.randn(n, 3, 3, generator=g))[0]
+    mu = (q * torch.linalg.det(q)[:, None, None]).contiguous().to(dev)  # rotations (det +1)
+    p = lib.plan("bwd", n, L, C, 1)
+    ws_bytes = lib.load().lv_group_action_bwd_workspace(n, L, C, 1)
+    ws = torch.empty(max(ws_bytes, 1), device=dev, dtype=torch.uint8)
+    gang, gF = torch.empty_like(ang), torch.empty_like(F)
+    call("lv_group_action_bwd", ptr(ang), ptr(F), 0, ptr(gout), ptr(gang), ptr(gF), n, L, C, transpose,
+         ptr(ws), ws_bytes, stream())
+    gmu, gv, gF2 = torch.empty_like(mu), torch.empty_like(v), torch.empty_like(F)
+    call("lv_fused_exp_action_bwd", ptr(mu), ptr(v), ptr(ang), ptr(F), ptr(gout), ptr(gmu), ptr(gv), ptr(gF2),
+         n, L, C, transpose, ptr(ws), ws_bytes, stream())
+    for k, t in (("mu", mu), ("gang", gang), ("gF", gF), ("gmu", gmu), ("gv", gv), ("gF2", gF2)):
+        out[f"{tag}_{k}"] = t.cpu().numpy()
+    out[f"{tag}_plan"] = np.array([p["tile"], p["segments"]])
+np.savez(sys.argv[2], **out)
+"""
+
+
+def test_action_bwd_ab_library_without_knobs_matches_product_bitwise(gpu_device, tmp_path):
+    """The A/B library (-DLV_AB_KNOBS) is a separate build of the backward's source: with no
+    knob set it gives the product library's gradients bit for bit -- lv_group_action_bwd and
+    lv_fused_exp_action_bwd with a mean, at l = 10, C = 10 for the one-group kernel (777
+    samples, transposed: 8 degree sets) and the persistent kernel (one group more than a
+    block per CU, ragged).  One child process per library, on the ctypes path."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(repo, "lie-vae_amd")
+    res = {}
+    for tag, name in (("product", "liblievae_hip.so"), ("ab", "liblievae_hip_ab.so")):
+        path = str(tmp_path / f"{tag}.npz")
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("LV_BWD_", "LV_SEG_", "LV_STAMPS"))}
+        env.update(LIEVAE_TORCH_OPS_LIB=str(tmp_path / "none.so"),
+                   LIEVAE_HIP_LIB=os.path.join(pkg, "lie_vae", name))
+        subprocess.run([sys.executable, "-c", _BWD_AB_SCRIPT, pkg, path], env=env, check=True, timeout=180)
+        res[tag] = np.load(path)
+    assert list(res["product"]["one_plan"]) == [1, 8] and int(res["product"]["persist_plan"][0]) == 3
+    assert sorted(res["ab"].files) == sorted(res["product"].files)
+    for key in res["product"].files:
+        assert np.array_equal(res["ab"][key], res["product"][key]), key
+    for key in ("one_gang", "one_gF", "one_gv", "one_gmu", "persist_gang", "persist_gF", "persist_gv"):
+        a = res["product"][key]
+        assert np.isfinite(a).all() and np.abs(a).max() > 0, key  # the kernels ran
+
+
 def test_exp_eazyz_vjp_matches_modular_bitwise(gpu_device):
     """lv_exp_eazyz_vjp (the fused path's prologue backward in one kernel) against the
     three modular kernels it replaces -- so3_exp_fwd / so3_sample_fwd, mat_to_eazyz_bwd,

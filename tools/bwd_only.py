@@ -77,9 +77,7 @@ def main():
     torch.cuda.synchronize(dev)
     us = e0.elapsed_time(e1) * 1e3 / (reps * 50)
     import hashlib
-    import numpy as np
     gf = gF.cpu().numpy()
-    np.save(os.path.join(REPO, "gpurun_out", f"bwd_only_gF_{B}_{os.environ.get('LV_BWD_VARIANT', 'd')}.npy"), gf)
     print(json.dumps({"batch": B, "fused": fused, "calls": reps * 50, "us_per_call": us,
                       "gF_sha": hashlib.sha1(gf.tobytes()).hexdigest()[:12],
                       "gang_sha": hashlib.sha1(gang.cpu().numpy().tobytes()).hexdigest()[:12],

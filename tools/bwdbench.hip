@@ -73,15 +73,23 @@ struct Out {
   std::vector<float> gang, ws;
 };
 
-static Out run_once(Kern k, dim3 g, dim3 b, size_t lds, const ActionBwdArgs& a, int64_t n, int64_t MC) {
+// chunked: the library kernel's chunk-major slabs (action_bwd.h), returned row-major like the
+// experiments' ([block][M*C]) for the comparison
+static Out run_once(Kern k, dim3 g, dim3 b, size_t lds, const ActionBwdArgs& a, int64_t n, int64_t MC,
+                    bool chunked = false) {
+  const size_t wsf = (size_t)g.x * slab_chunks(MC) * kSlabChunk;  // the workspace's floats
   CK(hipMemset(a.gang, 0xff, n * 12));
-  CK(hipMemset(a.ws_F, 0xff, (size_t)g.x * MC * 4));
+  CK(hipMemset(a.ws_F, 0xff, wsf * 4));
   hipLaunchKernelGGL(k, g, b, lds, 0, a);
   CK(hipGetLastError());
   CK(hipDeviceSynchronize());
+  std::vector<float> raw(wsf);
   Out o{std::vector<float>(n * 3), std::vector<float>((size_t)g.x * MC)};
   CK(hipMemcpy(o.gang.data(), a.gang, n * 12, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(o.ws.data(), a.ws_F, o.ws.size() * 4, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(raw.data(), a.ws_F, wsf * 4, hipMemcpyDeviceToHost));
+  for (size_t blk = 0; blk < g.x; ++blk)
+    for (int64_t e = 0; e < MC; ++e)
+      o.ws[blk * MC + e] = chunked ? raw[((e / kSlabChunk) * g.x + blk) * kSlabChunk + e % kSlabChunk] : raw[blk * MC + e];
   return o;
 }
 
@@ -108,7 +116,7 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&F, MC * 4));
   CK(hipMalloc(&gout, (size_t)n * MC * 4));
   CK(hipMalloc(&gang, n * 12));
-  CK(hipMalloc(&ws, (size_t)gx * MC * 4));
+  CK(hipMalloc(&ws, (size_t)gx * slab_chunks(MC) * kSlabChunk * 4));
   CK(hipMalloc(&gF, MC * 4));
   CK(hipMemcpy(ang, hang.data(), n * 12, hipMemcpyHostToDevice));
   CK(hipMemcpy(F, hF.data(), MC * 4, hipMemcpyHostToDevice));
@@ -121,6 +129,8 @@ int main(int argc, char** argv) {
   for (int nseg : {4, 3, 5, 6}) {
     ActionBwdArgs b = a;
     plan(nseg, b.seg_lo);
+    for (int k = 0; k < nseg; ++k)  // the library kernel's degree sets: the same ranges
+      for (int l = b.seg_lo[k]; l < b.seg_lo[k + 1]; ++l) b.seg_mask[k] |= 1u << l;
     int fp = 0;
     for (int k = 0; k < nseg; ++k) fp = std::max(fp, fseg_rows(b.seg_lo[k], b.seg_lo[k + 1]) * C);
     b.fpitch = (fp + 3) & ~3;
@@ -132,7 +142,7 @@ int main(int argc, char** argv) {
     for (int k = 0; k <= nseg; ++k) printf(" %d", b.seg_lo[k]);
     printf("\n");
     Kern lib = action_bwd_tile_kernel<L, C, kBwdFShared, false, 3>;
-    const Out ref = run_once(lib, g, bl, lds_lib, b, n, MC);
+    const Out ref = run_once(lib, g, bl, lds_lib, b, n, MC, true);
     const double tl = timeit(lib, g, bl, lds_lib, b, reps);
     printf("  lib tile kernel        %8.2f us  (%.0f GB/s incl. slabs)\n", tl, bytes / tl / 1e3);
     auto var = [&](Kern k, int v, const char* tag, bool exact) {

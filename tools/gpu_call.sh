@@ -15,7 +15,6 @@
 #   rehearse     the N-rank rehearsal (two ranks sharing the GPU, gloo)
 #   pmc-bwd      PMC passes of the training direction (tools/gpu_pmc_bwd.sh)
 #   ab-c5        config-5 bf16 tile-option variants (AB_C5 overrides the list)
-#   ab-bwd       backward knob variants (AB_KNOBS, AB_BATCHES override)
 # Every GPU step runs under its own time limit; a fault, abort or time-limit kill ends
 # the call there (no retries).
 set -u
@@ -86,10 +85,6 @@ for s in "$@"; do
       step ab_c5 900 bash tools/gpu_variants.sh "--lmax 20 --batch 8192 --dtype bf16 --sweep=65536" \
         ${AB_C5:-base= sw5=LV_TILE_SW=5}
       cat "$OUT/ab_c5.log" ;;
-    ab-bwd)  # backward knob variants (AB_KNOBS, tools/bwd_reduce_ab.py) at AB_BATCHES
-      step ab_bwd 900 env AB_KNOBS="${AB_KNOBS:-LV_BWD_REDUCE=0,LV_BWD_REDUCE=16,LV_BWD_REDUCE=3,LV_BWD_VARIANT=1,LV_BWD_REDUCE=0}" \
-        python tools/bwd_reduce_ab.py ${AB_BATCHES:-4096 512 65536}
-      cat "$OUT/ab_bwd.log" ;;
     *)
       echo "unknown step $s"; exit 2 ;;
   esac
