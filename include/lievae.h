@@ -235,6 +235,44 @@ int lv_so3_log_posterior_fwd(const float* v, const float* sigma, float* out, int
 int lv_so3_log_posterior_bwd(const float* v, const float* sigma, const float* gout, float* gv,
                              float* gsigma, int64_t ns, int64_t B, int k, void* stream);
 
+/* ---- Sreparameterize, the vMF latent on S^3: reparameterize.py:58-97 (csrc/vmf.hip) -----
+ * Latent modes vmf / vmfq.  m = 4 only.  mu (B,4) unit vectors, kappa (B) > 0 (the module
+ * gives softplus + 1 >= 1; 4 kappa^2 must stay finite in fp32).  All entry points:
+ * ns == 0 or B == 0 is LV_OK with nothing launched; negative sizes, trials outside 1..64 or a
+ * null pointer with work to do return LV_ERR_ARG before any launch.
+ *
+ * Sampler (Ulrich 1984 / Wood 1994, rejection from standard normals alone): noise
+ * (ns, B, 6 trials + 3); trial t owns g[0..3] = noise[6t .. 6t+3] and h[0..1] =
+ * noise[6t+4 .. 6t+5], the last three values are the tangent direction.  eps = (1 + g0/|g|)/2
+ * ~ Beta(3/2, 3/2); the trial is accepted iff 3 ln t - t + d >= -(h0^2 + h1^2)/2 with Wood's
+ * a, b, d and t = 2ab / (1 - (1 - b) eps).  The first accepted trial wins: accepted (ns, B)
+ * gets its index, or the value `trials` when none was accepted and the last proposal was
+ * used (probability <= 0.3125^trials).  One launch, a loop bounded by `trials`, no host sync.
+ * z (ns, B, 4) = the reflection taking e1 to mu applied to (w, sqrt(1 - w^2) v). */
+int lv_vmf_sample_fwd(const float* mu, const float* kappa, const float* noise, float* z,
+                      int32_t* accepted, int64_t ns, int64_t B, int trials, void* stream);
+/* Pathwise gradient (the accepted proposal held fixed; the acceptance-correction term of the
+ * rejection-reparameterisation estimator is left out): gz (ns, B, 4) -> gmu (B, 4), gkappa
+ * (B), each summed over the ns samples of a datum in ascending s by one thread (no atomics,
+ * bitwise reproducible).  Re-reads the accepted trial's six normals from noise. */
+int lv_vmf_sample_bwd(const float* mu, const float* kappa, const float* noise,
+                      const int32_t* accepted, const float* gz, float* gmu, float* gkappa,
+                      int64_t ns, int64_t B, int trials, void* stream);
+/* KL(vMF(mu, kappa) || U(S^3)) = kappa A + ln C + ln(2 pi^2), A = I_2 / I_1, ln C = ln kappa
+ * - 2 ln 2pi - ln I_1(kappa); kl (B).  Evaluated per datum in fp64 from exponentially scaled
+ * Bessel values (ascending series below kappa = 20, Hankel's asymptotic series above) and
+ * rounded once.  Backward: gkappa = gkl kappa A', A' = 1 - A^2 - 3A / kappa. */
+int lv_vmf_kl_fwd(const float* kappa, float* kl, int64_t B, void* stream);
+int lv_vmf_kl_bwd(const float* kappa, const float* gkl, float* gkappa, int64_t B, void* stream);
+/* log q(z) = ln C + kappa mu.z, evaluated as (ln C + kappa) - kappa |z - mu|^2 / 2 (no lost
+ * digits near the mode at large kappa; equal for unit mu and z); z (ns, B, 4), out (ns, B).
+ * Backward: gout (ns, B) -> gmu (B, 4), gkappa (B) (summed over s in ascending order), gz
+ * (ns, B, 4), mu and z treated as free 4-vectors. */
+int lv_vmf_log_prob_fwd(const float* mu, const float* kappa, const float* z, float* out,
+                        int64_t ns, int64_t B, void* stream);
+int lv_vmf_log_prob_bwd(const float* mu, const float* kappa, const float* z, const float* gout,
+                        float* gmu, float* gkappa, float* gz, int64_t ns, int64_t B, void* stream);
+
 /* ---- timing helper for bench.py: K back-to-back launches of the fused kernel
  * from C, so the host-side launch cost is not Python's.  Same arguments as
  * lv_fused_exp_action_fwd plus the repeat count. */

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "lv_common.h"
+#include "pointwise_launch.h"
 #include "so3_device.h"
 
 namespace lv {
@@ -23,27 +24,7 @@ void set_error(const char* fmt, ...) {
 }
 void clear_error() { g_err[0] = 0; }
 
-constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) {
-  int64_t b = (n + kBlock - 1) / kBlock;
-  if (b > 65536) b = 65536;  // grid-stride beyond
-  return dim3((unsigned)b);
-}
-
-#define LV_FOR_EACH(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-template <typename T, int K>
-__device__ __forceinline__ void ld(const T* p, T (&x)[K]) {
-#pragma unroll
-  for (int i = 0; i < K; ++i) x[i] = p[i];
-}
-template <typename T, int K>
-__device__ __forceinline__ void st(T* p, const T (&x)[K]) {
-#pragma unroll
-  for (int i = 0; i < K; ++i) p[i] = x[i];
-}
+// kBlock, grid_for, LV_FOR_EACH, ld / st: pointwise_launch.h (shared with vmf.hip)
 
 template <typename T>
 __global__ void so3_exp_fwd_k(const T* v, T* R, int64_t n) {

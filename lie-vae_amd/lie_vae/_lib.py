@@ -91,6 +91,13 @@ _SIGS["lv_equivariance_diff_bwd"] = [_P, _P, _P, _P, _P, _P, _I64, _P]
 _SIGS["lv_pair_sqdist_fwd"] = [_P, _P, _I64, _I, _P]
 _SIGS["lv_pair_sqdist_bwd"] = [_P, _P, _P, _I64, _I, _P]
 LV_ROTATE_DIRECT = 1  # include/lievae.h
+# vMF latent on S^3 (csrc/vmf.hip)
+_SIGS["lv_vmf_sample_fwd"] = [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]
+_SIGS["lv_vmf_sample_bwd"] = [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _P]
+_SIGS["lv_vmf_kl_fwd"] = [_P, _P, _I64, _P]
+_SIGS["lv_vmf_kl_bwd"] = [_P, _P, _P, _I64, _P]
+_SIGS["lv_vmf_log_prob_fwd"] = [_P, _P, _P, _P, _I64, _I64, _P]
+_SIGS["lv_vmf_log_prob_bwd"] = [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]
 _RESTYPES = {"lv_group_action_bwd_workspace": _SZ, "lv_last_error": ctypes.c_char_p,
              "lv_deconv4s2_packed_weight_elems": _SZ, "lv_deconv4s2_small_packed_weight_elems": _SZ,
              "lv_deconv4s2_packed_weight_elems_f32": _SZ,

@@ -200,6 +200,127 @@ class _SO3LogPosterior(torch.autograd.Function):
         return gv, gs, None
 
 
+# ------------------------------------------------------- vMF latent on S^3
+I32 = torch.int32
+
+
+class _VmfSample(torch.autograd.Function):
+    """z[s, b] ~ vMF(mu[b], kappa[b]) from the standard normals noise[s, b] (6 trials + 3 per
+    sample) -- reparameterize.py:90-93; also returns the accepted trial's index."""
+
+    @staticmethod
+    def forward(ctx, mu, kappa, noise):
+        mu, kappa, noise = _prep(mu), _prep(kappa), _prep(noise)
+        ns, B, W = noise.shape
+        trials = (W - 3) // 6
+        z = _empty((ns, B, 4), noise)
+        acc = _empty((ns, B), noise, I32)
+        call("lv_vmf_sample_fwd", ptr(mu), ptr(kappa), ptr(noise), ptr(z), ptr(acc), ns, B, trials,
+             stream())
+        ctx.save_for_backward(mu, kappa, noise, acc)
+        ctx.mark_non_differentiable(acc)
+        ctx.trials = trials
+        return z, acc
+
+    @staticmethod
+    def backward(ctx, gz, _gacc):
+        mu, kappa, noise, acc = ctx.saved_tensors
+        ns, B = acc.shape
+        new = torch.zeros_like if ns == 0 else torch.empty_like  # no samples: nothing is launched
+        gmu, gk = new(mu), new(kappa)
+        call("lv_vmf_sample_bwd", ptr(mu), ptr(kappa), ptr(noise), ptr(acc), ptr(_prep(gz)),
+             ptr(gmu), ptr(gk), ns, B, ctx.trials, stream())
+        return gmu, gk, None
+
+
+class _VmfKL(torch.autograd.Function):
+    """KL(vMF(., kappa) || U(S^3)) per datum -- reparameterize.py:79-82."""
+
+    @staticmethod
+    def forward(ctx, kappa):
+        kappa = _prep(kappa)
+        kl = torch.empty_like(kappa)
+        call("lv_vmf_kl_fwd", ptr(kappa), ptr(kl), kappa.shape[0], stream())
+        ctx.save_for_backward(kappa)
+        return kl
+
+    @staticmethod
+    def backward(ctx, g):
+        (kappa,) = ctx.saved_tensors
+        gk = torch.empty_like(kappa)
+        call("lv_vmf_kl_bwd", ptr(kappa), ptr(_prep(g)), ptr(gk), kappa.shape[0], stream())
+        return gk
+
+
+class _VmfLogProb(torch.autograd.Function):
+    """log q(z[s, b] | mu[b], kappa[b]) -- reparameterize.py:84-85."""
+
+    @staticmethod
+    def forward(ctx, mu, kappa, z):
+        mu, kappa, z = _prep(mu), _prep(kappa), _prep(z)
+        ns, B = z.shape[0], z.shape[1]
+        out = _empty((ns, B), z)
+        call("lv_vmf_log_prob_fwd", ptr(mu), ptr(kappa), ptr(z), ptr(out), ns, B, stream())
+        ctx.save_for_backward(mu, kappa, z)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mu, kappa, z = ctx.saved_tensors
+        ns, B = z.shape[0], z.shape[1]
+        new = torch.zeros_like if ns == 0 else torch.empty_like
+        gmu, gk, gz = new(mu), new(kappa), torch.empty_like(z)
+        call("lv_vmf_log_prob_bwd", ptr(mu), ptr(kappa), ptr(z), ptr(_prep(g)), ptr(gmu), ptr(gk),
+             ptr(gz), ns, B, stream())
+        return gmu, gk, gz
+
+
+VMF_MAX_TRIALS = 64  # csrc/vmf.hip kVmfMaxTrials
+_VMF_ACCEPTED = None
+
+
+def _check_vmf(mu, kappa, B, what):
+    assert tuple(mu.shape) == (B, 4), f"{what}: mu must be ({B},4), got {tuple(mu.shape)}"
+    assert tuple(kappa.shape) == (B,), f"{what}: kappa must be ({B},), got {tuple(kappa.shape)}"
+
+
+def vmf_sample(mu, kappa, noise):
+    """mu (B,4) unit, kappa (B), noise (ns, B, 6 T + 3) standard normals -> z (ns, B, 4) on
+    S^3; T = the number of rejection trials, 1..64, read off the noise's width.  Differentiable
+    in mu and kappa (pathwise).  vmf_last_accepted() gives the accepted trial per sample."""
+    global _VMF_ACCEPTED
+    assert noise.dim() == 3, f"vmf_sample: noise must be (ns, B, 6T+3), got {tuple(noise.shape)}"
+    W = noise.shape[2]
+    assert W >= 9 and (W - 3) % 6 == 0 and (W - 3) // 6 <= VMF_MAX_TRIALS, \
+        f"vmf_sample: noise width must be 6T+3 with 1 <= T <= {VMF_MAX_TRIALS}, got {W}"
+    _check_vmf(mu, kappa, noise.shape[1], "vmf_sample")
+    _lib.require_device(mu, kappa, noise)
+    z, _VMF_ACCEPTED = _VmfSample.apply(mu, kappa, noise.detach())
+    return z
+
+
+def vmf_last_accepted():
+    """(ns, B) int32 of the last vmf_sample call: the index of the accepted trial, or T where
+    none of the T was accepted and the last proposal was used.  Carries no gradient."""
+    return _VMF_ACCEPTED
+
+
+def vmf_kl(kappa):
+    """kappa (B) -> KL(vMF || uniform on S^3) (B); differentiable."""
+    assert kappa.dim() == 1, f"vmf_kl: kappa must be (B,), got {tuple(kappa.shape)}"
+    _lib.require_device(kappa)
+    return _VmfKL.apply(kappa)
+
+
+def vmf_log_prob(mu, kappa, z):
+    """mu (B,4), kappa (B), z (ns, B, 4) -> log q(z) (ns, B); differentiable in all three."""
+    assert z.dim() == 3 and z.shape[2] == 4, \
+        f"vmf_log_prob: z must be (ns, B, 4), got {tuple(z.shape)}"
+    _check_vmf(mu, kappa, z.shape[1], "vmf_log_prob")
+    _lib.require_device(mu, kappa, z)
+    return _VmfLogProb.apply(mu, kappa, z)
+
+
 # ------------------------------------------------------------ group action
 _WS_BYTES = {}   # (n, L, C, shared F) -> lv_group_action_bwd_workspace
 _WS_BUF = {}     # (device index, raw stream) -> cached uint8 workspace (eager calls only)

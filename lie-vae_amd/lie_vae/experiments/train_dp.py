@@ -281,7 +281,7 @@ class DPTrainer:
 
     # the per-forward samples the latent modules and the VAE keep on ``self``
     # (reparameterize.py:41,94-95,192; vae.py:103)
-    _SAMPLE_FIELDS = ("z", "v", "mu_lie", "sigma", "mu")
+    _SAMPLE_FIELDS = ("z", "v", "mu_lie", "sigma", "mu", "k")  # k: the vMF module's kappa
 
     def _drop_autograd_refs(self):
         """The model keeps its last sample (VAE.z, the latent modules' z / v / mu_lie /

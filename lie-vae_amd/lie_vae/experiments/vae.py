@@ -120,7 +120,9 @@ class VAE(nn.Module):
         if self.r_callback is not None:
             return [r(f(h), n) for r, f in zip(self.reparameterize, self.r_callback)]
         if eps is not None:
-            return [r(h, n, eps=eps) for r in self.reparameterize]
+            # the vMF module's injected noise is (n, B, 6·trials + 3) and is named `noise`
+            return [r(h, n, noise=eps) if isinstance(r, Sreparameterize) else r(h, n, eps=eps)
+                    for r in self.reparameterize]
         return [r(h, n) for r in self.reparameterize]
 
     def kl(self):

@@ -9,11 +9,13 @@ Same module names, constructor arguments, stateful attributes (``sigma``, ``z``,
 * z = μ·exp(v)                            (SO3reparameterize.nsample, :269-273)
 * 21-term wrapped log-density + logsumexp (SO3reparameterize.log_posterior, :233-263)
 * mean maps rodrigues / quaternion / S2S1 / fp64 S2S2 (:148-197)
+* the vMF latent on S³: rejection sampler, KL, log-density (Sreparameterize, :58-97)
 
 Extension (superset of the reference API): ``forward(x, n, eps=None)`` accepts an
 injected standard-normal ε of shape (n, B, z_dim), used by the parity tests; by
 default ε is drawn on the device with ``torch.randn`` as the reference's
-``Normal.sample`` does.
+``Normal.sample`` does.  ``Sreparameterize`` names its injected normals ``noise``
+(n, B, 6·trials + 3).
 """
 import math
 
@@ -70,12 +72,64 @@ class Nreparameterize(nn.Module):
 
 
 class Sreparameterize(nn.Module):
-    """vMF latent (reparameterize.py:58-97) needs the third-party
-    ``hyperspherical_vae_pytorch`` package, absent here and outside the SO(3) hot path."""
+    """von Mises–Fisher latent on S³ (latent modes ``vmf`` / ``vmfq``) — reparameterize.py:58-97.
+
+    The reference builds it on the third-party ``hyperspherical_vae_pytorch``; here the
+    sampler, KL(vMF ‖ uniform) and the log-density are HIP kernels (csrc/vmf.hip) written from
+    the published definitions.  Only ``z_dim == 4`` exists, the one size the
+    reference builds.  Same constructor, attributes (``mu`` (B, 4) unit, ``k`` (B, 1) =
+    softplus + 1, ``z``, ``return_means``) and methods as the reference.
+
+    Extension: ``forward(x, n, noise=None)`` accepts injected standard normals of shape
+    (n, B, 6·trials + 3) — per rejection trial four normals for the proposal and two for the
+    acceptance draw, then three for the tangent direction; ``None`` draws them with one
+    ``torch.randn`` on the device.  The sampler runs ``trials`` (attribute, default 16,
+    at most 64) bounded rejection rounds in one launch with no host sync, so the step stays
+    graph-capturable; ``_ops.vmf_last_accepted()`` reports the accepted round per sample.
+    The pathwise gradient leaves out the rejection sampler's acceptance-correction term
+    (DESIGN.md §8)."""
 
     def __init__(self, input_dim, z_dim):
-        raise ImportError("Sreparameterize requires hyperspherical_vae_pytorch (out of scope, "
-                          "see DESIGN.md)")
+        super().__init__()
+        if z_dim != 4:
+            raise NotImplementedError(f"Sreparameterize: only the vMF latent on S³ (z_dim = 4) "
+                                      f"is implemented, got z_dim = {z_dim}")
+        self.input_dim = input_dim
+        self.z_dim = z_dim
+        self.k_linear = nn.Linear(input_dim, 1)
+        self.mu_linear = nn.Linear(input_dim, z_dim)
+        self.return_means = False
+        self.trials = 16
+        self.mu, self.k, self.z = None, None, None
+
+    def forward(self, x, n=1, noise=None):
+        self.mu = self.mu_linear(x)
+        self.mu = self.mu / self.mu.norm(p=2, dim=-1, keepdim=True)
+        self.k = F.softplus(self.k_linear(x)) + 1
+        self.z = self.nsample(n=n, noise=noise)
+        return self.z
+
+    def kl(self):
+        return _ops.vmf_kl(self.k.reshape(-1))
+
+    def log_posterior(self):
+        return _ops.vmf_log_prob(self.mu, self.k.reshape(-1), self.z)
+
+    def log_prior(self):
+        # -ln of the area 2π² of S³, a device fill (capturable, no host-to-device copy)
+        prior = self.z.new_full((1,), -math.log(2 * math.pi ** 2))
+        return prior.expand_as(self.z[..., 0])
+
+    def nsample(self, n=1, noise=None):
+        if self.return_means:
+            return self.mu.expand(n, -1, -1)
+        if noise is None:
+            noise = torch.randn((n, self.mu.shape[0], 6 * self.trials + 3),
+                                device=self.mu.device, dtype=self.mu.dtype)
+        return _ops.vmf_sample(self.mu, self.k.reshape(-1), noise)
+
+    def deterministic(self):
+        self.return_means = True
 
 
 class N0reparameterize(nn.Module):
