@@ -120,6 +120,49 @@ int lv_s2s1_fwd_f64(const double* axis, const double* cs, double* R, int64_t n, 
 int lv_s2s1_bwd_f64(const double* axis, const double* cs, const double* gR, double* gaxis,
                     double* gcs, int64_t n, void* stream);
 
+/* ---- so(3) log map: lie_tools.py:100-109 `log_map`, batched and stable -------
+ * v = log(R): R (n,3,3) -> v (n,3), |v| in [0, pi].  The reference's expression
+ * theta / sin(theta) * (R - R^T)/2 with theta = acos((tr R - 1)/2) is NaN at the identity
+ * and has no digits near pi; here theta = atan2(|w|, c) with w = vee(R - R^T)/2 and
+ * c = (tr R - 1)/2, v = (theta/|w|) w for c >= 0 (a series near 0: the identity gives exactly
+ * 0), and for c < 0 the axis comes from the symmetric part (R + R^T)/2 = c I + (1 - c) a a^T,
+ * signed so that a.w >= 0.  At theta = pi exactly (w = 0) both signs are logs of R: the
+ * component of largest magnitude is made positive.
+ * Backward: the input is a rotation, so the gradient is the tangent-space gradient at R,
+ * gR = R hat(u), u = J_r^-T(v) gv / 2, J_r^-1(v) = I + hat(v)/2 + kappa hat(v)^2,
+ * kappa = 1/theta^2 - cot(theta/2)/(2 theta); finite up to pi.  Its component normal to SO(3)
+ * is zero by definition: composed with a parametrisation that stays in SO(3) it gives the
+ * parameter gradients autograd would find through any other formula of the log.
+ * Negative sizes, or a null pointer with work to do, return LV_ERR_ARG before any launch;
+ * empty sizes return LV_OK with nothing launched. */
+int lv_so3_log_fwd(const float* R, float* v, int64_t n, void* stream);
+int lv_so3_log_bwd(const float* R, const float* gv, float* gR, int64_t n, void* stream);
+/* inverse of lv_so3_sample_fwd: v[s,b] = log(mu[b]^T z[s,b]); mu (B,3,3), z (ns,B,3,3),
+ * v (ns,B,3).  Backward: gz = z hat(u), gmu[b] = sum_s mu hat(-Q u) with Q = mu^T z, summed
+ * over s in ascending order by one thread per b (bitwise reproducible); ns == 0 zero-fills
+ * gmu. */
+int lv_so3_rel_log_fwd(const float* mu, const float* z, float* v, int64_t ns, int64_t B,
+                       void* stream);
+int lv_so3_rel_log_bwd(const float* mu, const float* z, const float* gv, float* gmu, float* gz,
+                       int64_t ns, int64_t B, void* stream);
+/* rotation angle of A^T B (the geodesic distance): (n,3,3),(n,3,3) -> (n), in [0, pi].
+ * Backward: gB = B hat(gtheta a / 2), gA = -A hat(gtheta a / 2), a the unit axis of
+ * log(A^T B); exactly 0 where theta = 0 (the kink of a norm). */
+int lv_so3_angle_fwd(const float* A, const float* B, float* theta, int64_t n, void* stream);
+int lv_so3_angle_bwd(const float* A, const float* B, const float* gtheta, float* gA, float* gB,
+                     int64_t n, void* stream);
+/* fp64 twins (the per-sample maps follow their input dtype) */
+int lv_so3_log_fwd_f64(const double* R, double* v, int64_t n, void* stream);
+int lv_so3_log_bwd_f64(const double* R, const double* gv, double* gR, int64_t n, void* stream);
+int lv_so3_rel_log_fwd_f64(const double* mu, const double* z, double* v, int64_t ns, int64_t B,
+                           void* stream);
+int lv_so3_rel_log_bwd_f64(const double* mu, const double* z, const double* gv, double* gmu,
+                           double* gz, int64_t ns, int64_t B, void* stream);
+int lv_so3_angle_fwd_f64(const double* A, const double* B, double* theta, int64_t n,
+                         void* stream);
+int lv_so3_angle_bwd_f64(const double* A, const double* B, const double* gtheta, double* gA,
+                         double* gB, int64_t n, void* stream);
+
 /* ---- s2s2_gram_schmidt, fp64: lie_tools.py:81-89 (S2S2Mean, reparameterize.py:184-197)
  * Crosses along the last axis (the reference's torch.cross without dim is
  * wrong at batch 3; documented deviation). */

@@ -241,6 +241,113 @@ __global__ void s2s2_bwd_k(const double* v1, const double* v2, const double* gR,
   }
 }
 
+// ---------------------------------------------------------------- so(3) log family
+// v = log R (so3_device.h so3_log_polar); backward on the tangent space, gR = R hat(u).
+template <typename T>
+__global__ void so3_log_fwd_k(const T* R, T* v, int64_t n) {
+  LV_FOR_EACH(i, n) {
+    T r[9];
+    ld(R + i * 9, r);
+    LogPolar<T> p;
+    so3_log_polar(r, p);
+    st(v + i * 3, p.v);
+  }
+}
+template <typename T>
+__global__ void so3_log_bwd_k(const T* R, const T* gv, T* gR, int64_t n) {
+  LV_FOR_EACH(i, n) {
+    T r[9], g[3], u[3], o[9];
+    ld(R + i * 9, r);
+    ld(gv + i * 3, g);
+    LogPolar<T> p;
+    so3_log_polar(r, p);
+    so3_log_tangent(p, g, u);
+    mul_hat(r, u, o);
+    st(gR + i * 9, o);
+  }
+}
+
+// v[s,b] = log(mu[b]^T z[s,b]): the inverse of so3_sample_fwd_k
+template <typename T>
+__global__ void so3_rel_log_fwd_k(const T* mu, const T* z, T* v, int64_t ns, int64_t B) {
+  LV_FOR_EACH(i, ns * B) {
+    const int64_t b = i % B;
+    T m[9], zz[9], q[9];
+    ld(mu + b * 9, m);
+    ld(z + i * 9, zz);
+    matmul3_tn(m, zz, q);
+    LogPolar<T> p;
+    so3_log_polar(q, p);
+    st(v + i * 3, p.v);
+  }
+}
+// gz[s,b] = z hat(u); gmu[b] = sum_s mu hat(-Q u), Q = mu^T z (fixed order, one thread per b)
+// (launch bounds: every launch here uses kBlock threads; without them the fp64 twin is held to
+// the 128 registers of a 1,024-thread block and spills)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) so3_rel_log_bwd_k(const T* mu, const T* z, const T* gv, T* gmu, T* gz,
+                                  int64_t ns, int64_t B) {
+  LV_FOR_EACH(b, B) {
+    T m[9], acc[3];
+    ld(mu + b * 9, m);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = T(0);
+    for (int64_t s = 0; s < ns; ++s) {
+      const int64_t i = s * B + b;
+      T zz[9], q[9], g[3], u[3], o[9];
+      ld(z + i * 9, zz);
+      ld(gv + i * 3, g);
+      matmul3_tn(m, zz, q);
+      LogPolar<T> p;
+      so3_log_polar(q, p);
+      so3_log_tangent(p, g, u);
+      mul_hat(zz, u, o);
+      st(gz + i * 9, o);
+      // mu hat(.) is linear: sum the vectors -Q u, one product with mu at the end
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        acc[k] -= (q[k * 3 + 0] * u[0] + q[k * 3 + 1] * u[1]) + q[k * 3 + 2] * u[2];
+    }
+    T om[9];
+    mul_hat(m, acc, om);
+    st(gmu + b * 9, om);
+  }
+}
+
+// theta[i] = rotation angle of A[i]^T B[i]; gB = B hat(gtheta a / 2), gA = -A hat(gtheta a / 2)
+template <typename T>
+__global__ void so3_angle_fwd_k(const T* A, const T* Bm, T* theta, int64_t n) {
+  LV_FOR_EACH(i, n) {
+    T a[9], b[9], q[9];
+    ld(A + i * 9, a);
+    ld(Bm + i * 9, b);
+    matmul3_tn(a, b, q);
+    LogPolar<T> p;
+    so3_log_polar(q, p);
+    theta[i] = p.th;
+  }
+}
+template <typename T>
+__global__ void so3_angle_bwd_k(const T* A, const T* Bm, const T* gtheta, T* gA, T* gB, int64_t n) {
+  LV_FOR_EACH(i, n) {
+    T a[9], b[9], q[9], u[3], oa[9], ob[9];
+    ld(A + i * 9, a);
+    ld(Bm + i * 9, b);
+    matmul3_tn(a, b, q);
+    LogPolar<T> p;
+    so3_log_polar(q, p);
+    const T h = T(0.5) * gtheta[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u[k] = h * p.a[k];
+    mul_hat(b, u, ob);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) u[k] = -u[k];
+    mul_hat(a, u, oa);
+    st(gA + i * 9, oa);
+    st(gB + i * 9, ob);
+  }
+}
+
 // ---------------------------------------------------------------- N0 + SO(3) density
 // softplus(x) = log1p(exp(x)), identity above threshold 20 (torch defaults).
 __global__ void softplus_fwd_k(const float* h, float* s, int64_t n) {
@@ -630,6 +737,52 @@ int lv_s2s2_bwd_f64(const double* v1, const double* v2, const double* gR, double
   LV_PTRS(v1 && v2 && gR && gv1 && gv2);
   LV_LAUNCH1(s2s2_bwd_k, n, v1, v2, gR, gv1, gv2, n);
 }
+// so(3) log family, fp32 and the fp64 twins (the maps follow their input dtype): one body.
+#define LV_SO3_LOG_ENTRIES(T, SUF)                                                              \
+  int lv_so3_log_fwd##SUF(const T* R, T* v, int64_t n, void* stream) {                          \
+    LV_CHECK_ARG(n >= 0, "n must be >= 0");                                                     \
+    LV_PTRS(R && v);                                                                            \
+    LV_LAUNCH1(so3_log_fwd_k<T>, n, R, v, n);                                                   \
+  }                                                                                             \
+  int lv_so3_log_bwd##SUF(const T* R, const T* gv, T* gR, int64_t n, void* stream) {            \
+    LV_CHECK_ARG(n >= 0, "n must be >= 0");                                                     \
+    LV_PTRS(R && gv && gR);                                                                     \
+    LV_LAUNCH1(so3_log_bwd_k<T>, n, R, gv, gR, n);                                              \
+  }                                                                                             \
+  int lv_so3_rel_log_fwd##SUF(const T* mu, const T* z, T* v, int64_t ns, int64_t B,             \
+                              void* stream) {                                                   \
+    LV_CHECK_ARG(ns >= 0 && B >= 0, "ns and B must be >= 0");                                   \
+    const int64_t n = ns * B;                                                                   \
+    LV_PTRS(mu && z && v);                                                                      \
+    LV_LAUNCH1(so3_rel_log_fwd_k<T>, n, mu, z, v, ns, B);                                       \
+  }                                                                                             \
+  int lv_so3_rel_log_bwd##SUF(const T* mu, const T* z, const T* gv, T* gmu, T* gz, int64_t ns,  \
+                              int64_t B, void* stream) {                                        \
+    LV_CHECK_ARG(ns >= 0 && B >= 0, "ns and B must be >= 0");                                   \
+    const int64_t n = B;                                                                        \
+    LV_CHECK_ARG(n == 0 || (mu && gmu && (ns == 0 || (z && gv && gz))), "null pointer argument"); \
+    if (ns == 0 && B > 0) {                                                                     \
+      clear_error();                                                                            \
+      (void)hipMemsetAsync(gmu, 0, sizeof(T) * 9 * B, (hipStream_t)stream);                     \
+      return LV_OK;                                                                             \
+    }                                                                                           \
+    LV_LAUNCH1(so3_rel_log_bwd_k<T>, n, mu, z, gv, gmu, gz, ns, B);                             \
+  }                                                                                             \
+  int lv_so3_angle_fwd##SUF(const T* A, const T* B, T* theta, int64_t n, void* stream) {        \
+    LV_CHECK_ARG(n >= 0, "n must be >= 0");                                                     \
+    LV_PTRS(A && B && theta);                                                                   \
+    LV_LAUNCH1(so3_angle_fwd_k<T>, n, A, B, theta, n);                                          \
+  }                                                                                             \
+  int lv_so3_angle_bwd##SUF(const T* A, const T* B, const T* gtheta, T* gA, T* gB, int64_t n,   \
+                            void* stream) {                                                     \
+    LV_CHECK_ARG(n >= 0, "n must be >= 0");                                                     \
+    LV_PTRS(A && B && gtheta && gA && gB);                                                      \
+    LV_LAUNCH1(so3_angle_bwd_k<T>, n, A, B, gtheta, gA, gB, n);                                 \
+  }
+LV_SO3_LOG_ENTRIES(float, )
+LV_SO3_LOG_ENTRIES(double, _f64)
+#undef LV_SO3_LOG_ENTRIES
+
 int lv_softplus_fwd(const float* h, float* sigma, int64_t n, void* stream) {
   LV_PTRS(h && sigma);
   LV_LAUNCH1(softplus_fwd_k, n, h, sigma, n);

@@ -148,6 +148,111 @@ __device__ __forceinline__ void matmul3_nt(const T A[9], const T B[9], T C[9]) {
                      A[i * 3 + 2] * B[j * 3 + 2];
 }
 
+// ------------------------------------------------------------------ so(3) log
+// lie_tools.py:100-109 (log_map) gives theta / sin(theta) * (R - R^T)/2 with theta = acos of
+// the trace: NaN at the identity, and no digits left near theta = pi, where R - R^T vanishes
+// and acos of an fp32 cosine is useless (as for beta above).  Here, per sample:
+//   w = vee(R - R^T)/2, s = |w| = sin(theta), c = (tr R - 1)/2, theta = atan2(s, c) in [0, pi].
+//   c >= 0: v = (theta/s) w; below s = kLogSeriesS, theta/s = asin(s)/s by its series, so R = I
+//           gives v = 0 exactly.
+//   c <  0: the axis from the symmetric part S = (R + R^T)/2 = c I + (1 - c) a a^T: the largest
+//           a_i^2 = (S_ii - c)/(1 - c) (>= 1/3, so the root and the division are well
+//           conditioned), the other two components from row i of S, renormalised, the sign such
+//           that a.w >= 0; v = theta a.  At theta = pi exactly (w = 0) both signs are logs of R:
+//           a_i > 0 is kept, i.e. the component of largest magnitude is positive.
+// LogPolar also carries the unit axis (0 where s == 0 on the c >= 0 side: the identity).
+constexpr double kLogSeriesS = 0.03;
+constexpr double kKappaSeriesTh = 0.25;
+
+template <typename T>
+struct LogPolar {
+  T th, v[3], a[3];
+};
+
+template <typename T>
+__device__ __forceinline__ void so3_log_polar(const T r[9], LogPolar<T>& p) {
+  // scalars and selects throughout: no small array is indexed or passed by address, so
+  // nothing lands in scratch memory
+  const T w0 = T(0.5) * (r[7] - r[5]), w1 = T(0.5) * (r[2] - r[6]), w2 = T(0.5) * (r[3] - r[1]);
+  const T s = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+  const T c = T(0.5) * (((r[0] + r[4]) + r[8]) - T(1.));
+  const T th = atan2(s, c);
+  T a0, a1, a2, v0, v1, v2;
+  if (c >= T(0.)) {
+    const T s2 = s * s;
+    const T k = s < T(kLogSeriesS)
+                    ? T(1.) + s2 * (T(1. / 6.) + s2 * (T(3. / 40.) + s2 * T(15. / 336.)))
+                    : th / s;
+    const T inv = s > T(0.) ? T(1.) / s : T(0.);
+    v0 = k * w0; v1 = k * w1; v2 = k * w2;
+    a0 = w0 * inv; a1 = w1 * inv; a2 = w2 * inv;
+  } else {
+    const T omc = T(1.) - c;
+    const T d0 = (r[0] - c) / omc, d1 = (r[4] - c) / omc, d2 = (r[8] - c) / omc;
+    const int i = (d0 >= d1 && d0 >= d2) ? 0 : (d1 >= d2 ? 1 : 2);
+    const T ai = sqrt(i == 0 ? d0 : (i == 1 ? d1 : d2));
+    const T den = omc * ai;
+    const T s01 = T(0.5) * (r[1] + r[3]), s02 = T(0.5) * (r[2] + r[6]), s12 = T(0.5) * (r[5] + r[7]);
+    // row i of S over (1 - c) a_i, a_i itself on the diagonal
+    const T b0 = i == 0 ? ai : (i == 1 ? s01 : s02) / den;
+    const T b1 = i == 1 ? ai : (i == 0 ? s01 : s12) / den;
+    const T b2 = i == 2 ? ai : (i == 0 ? s02 : s12) / den;
+    const T nrm = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+    const T sgn = (b0 * w0 + b1 * w1) + b2 * w2 < T(0.) ? -T(1.) : T(1.);
+    a0 = sgn * (b0 / nrm); a1 = sgn * (b1 / nrm); a2 = sgn * (b2 / nrm);
+    v0 = th * a0; v1 = th * a1; v2 = th * a2;
+  }
+  p.th = th;
+  p.v[0] = v0; p.v[1] = v1; p.v[2] = v2;
+  p.a[0] = a0; p.a[1] = a1; p.a[2] = a2;
+}
+
+// kappa(theta) = 1/theta^2 - cot(theta/2) / (2 theta): 1/12 at 0 (series below
+// kKappaSeriesTh, where the two terms cancel), 1/pi^2 at pi.
+template <typename T>
+__device__ __forceinline__ T so3_kappa(T th) {
+  if (th < T(kKappaSeriesTh)) {
+    const T t2 = th * th;
+    return T(1. / 12.) +
+           t2 * (T(1. / 720.) + t2 * (T(1. / 30240.) + t2 * (T(1. / 1209600.) + t2 * T(1. / 47900160.))));
+  }
+  T sh, ch;
+  lv_sincos(T(0.5) * th, &sh, &ch);
+  return T(1.) / (th * th) - ch / ((T(2.) * th) * sh);
+}
+
+// Backward of the log.  The input is a rotation, so the gradient is defined on the tangent
+// space of SO(3) at R: with log(R exp(xi)) = v + J_r^-1(v) xi + O(xi^2) and
+// J_r^-1(v) = I + hat(v)/2 + kappa(|v|) hat(v)^2, the gradient is gR = R hat(u),
+// u = J_r^-T(v) gv / 2 = (gv - v x gv / 2 + kappa v x (v x gv)) / 2, finite up to theta = pi.
+// Its component normal to SO(3) is zero by definition; composed with any parametrisation that
+// stays in SO(3) it gives the parameter gradients autograd finds through any other formula.
+template <typename T>
+__device__ __forceinline__ void cross3(const T a[3], const T b[3], T c[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+template <typename T>
+__device__ __forceinline__ void so3_log_tangent(const LogPolar<T>& p, const T gv[3], T u[3]) {
+  T x1[3], x2[3];
+  cross3(p.v, gv, x1);
+  cross3(p.v, x1, x2);
+  const T kap = so3_kappa(p.th);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) u[j] = T(0.5) * ((gv[j] - T(0.5) * x1[j]) + kap * x2[j]);
+}
+// G = R hat(u)
+template <typename T>
+__device__ __forceinline__ void mul_hat(const T r[9], const T u[3], T g[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    g[i * 3 + 0] = r[i * 3 + 1] * u[2] - r[i * 3 + 2] * u[1];
+    g[i * 3 + 1] = r[i * 3 + 2] * u[0] - r[i * 3 + 0] * u[2];
+    g[i * 3 + 2] = r[i * 3 + 0] * u[1] - r[i * 3 + 1] * u[0];
+  }
+}
+
 // ----------------------------------------------- group_matrix_to_quaternions
 // lie_tools.py:112-157: 4-case trace method, eps 1e-6, case = first argmax.
 template <typename T>

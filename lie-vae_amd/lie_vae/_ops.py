@@ -75,8 +75,10 @@ MAT_TO_QUAT = ("lv_mat_to_quat_fwd", "lv_mat_to_quat_bwd", (3, 3), (4,))
 QUAT_TO_EAZYZ = ("lv_quat_to_eazyz_fwd", "lv_quat_to_eazyz_bwd", (4,), (3,))
 MAT_TO_EAZYZ = ("lv_mat_to_eazyz_fwd", "lv_mat_to_eazyz_bwd", (3, 3), (3,))
 SOFTPLUS = ("lv_softplus_fwd", "lv_softplus_bwd", (), ())
+SO3_LOG = ("lv_so3_log_fwd", "lv_so3_log_bwd", (3, 3), (3,))
 # maps with fp64 twins
-_F64_MAPS = {s[0] for s in (SO3_EXP, QUAT_TO_MAT, MAT_TO_QUAT, QUAT_TO_EAZYZ, MAT_TO_EAZYZ)}
+_F64_MAPS = {s[0] for s in (SO3_EXP, QUAT_TO_MAT, MAT_TO_QUAT, QUAT_TO_EAZYZ, MAT_TO_EAZYZ,
+                            SO3_LOG)}
 
 
 def unary(x, spec):
@@ -152,6 +154,77 @@ class _SO3Sample(torch.autograd.Function):
         call(_k("lv_so3_sample_bwd", ctx.dt), ptr(mu), ptr(v), ptr(gz), ptr(gmu), ptr(gv), ns,
              B, stream())
         return gmu, gv
+
+
+class _SO3RelLog(torch.autograd.Function):
+    """v[s, b] = log(mu[b]^T z[s, b]), the inverse of _SO3Sample; tangent-space gradients
+    (include/lievae.h lv_so3_rel_log_bwd)."""
+
+    @staticmethod
+    def forward(ctx, mu, z):
+        dt = _map_dtype(mu, z)
+        mu = _prep(mu, dt)
+        z = _prep(z, dt)
+        ns, B = z.shape[0], z.shape[1]
+        v = _empty((ns, B, 3), z, dt)
+        call(_k("lv_so3_rel_log_fwd", dt), ptr(mu), ptr(z), ptr(v), ns, B, stream())
+        ctx.save_for_backward(mu, z)
+        ctx.dt = dt
+        return v
+
+    @staticmethod
+    def backward(ctx, gv):
+        mu, z = ctx.saved_tensors
+        ns, B = z.shape[0], z.shape[1]
+        gv = _prep(gv, ctx.dt)
+        gmu, gz = torch.empty_like(mu), torch.empty_like(z)
+        call(_k("lv_so3_rel_log_bwd", ctx.dt), ptr(mu), ptr(z), ptr(gv), ptr(gmu), ptr(gz), ns,
+             B, stream())
+        return gmu, gz
+
+
+def so3_rel_log(mu, z):
+    """mu (B,3,3), z (ns,B,3,3) rotations -> v (ns,B,3) with z = mu exp(v), |v| <= pi;
+    differentiable in both."""
+    assert z.dim() == 4 and tuple(z.shape[2:]) == (3, 3), \
+        f"so3_rel_log: z must be (ns, B, 3, 3), got {tuple(z.shape)}"
+    assert tuple(mu.shape) == (z.shape[1], 3, 3), \
+        f"so3_rel_log: mu must be ({z.shape[1]},3,3), got {tuple(mu.shape)}"
+    _lib.require_device(mu, z)
+    return _SO3RelLog.apply(mu, z)
+
+
+class _SO3Angle(torch.autograd.Function):
+    """theta = rotation angle of A^T B, in [0, pi] (include/lievae.h lv_so3_angle_fwd)."""
+
+    @staticmethod
+    def forward(ctx, A, B):
+        dt = _map_dtype(A, B)
+        a, lead, n = _flat(_prep(A, dt), (3, 3))
+        b, _, _ = _flat(_prep(B, dt), (3, 3))
+        th = _empty((n,), a, dt)
+        call(_k("lv_so3_angle_fwd", dt), ptr(a), ptr(b), ptr(th), n, stream())
+        ctx.save_for_backward(a, b)
+        ctx.lead, ctx.n, ctx.dt = lead, n, dt
+        return th.reshape(lead)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        gf = _prep(g, ctx.dt).reshape(ctx.n)
+        ga, gb = torch.empty_like(a), torch.empty_like(b)
+        call(_k("lv_so3_angle_bwd", ctx.dt), ptr(a), ptr(b), ptr(gf), ptr(ga), ptr(gb), ctx.n,
+             stream())
+        return ga.reshape(*ctx.lead, 3, 3), gb.reshape(*ctx.lead, 3, 3)
+
+
+def so3_angle(A, B):
+    """A, B (...,3,3) rotations of one shape -> the rotation angle of A^T B (...), in [0, pi];
+    differentiable in both (gradient 0 where the angle is 0)."""
+    assert A.dim() >= 2 and tuple(A.shape[-2:]) == (3, 3) and A.shape == B.shape, \
+        f"so3_angle: A and B must be (...,3,3) of one shape, got {tuple(A.shape)} and {tuple(B.shape)}"
+    _lib.require_device(A, B)
+    return _SO3Angle.apply(A, B)
 
 
 class _N0Sample(torch.autograd.Function):

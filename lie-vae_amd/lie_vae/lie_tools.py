@@ -20,7 +20,7 @@ __all__ = [
     "s2s2_gram_schmidt", "vector_to_eazyz", "log_map", "group_matrix_to_quaternions",
     "quaternions_to_eazyz", "group_matrix_to_eazyz", "quaternions_to_group_matrix",
     "wigner_d_matrix", "block_wigner_matrix_multiply", "random_quaternions",
-    "random_group_matrices",
+    "random_group_matrices", "so3_log", "geodesic_distance",
 ]
 
 
@@ -67,10 +67,37 @@ def vector_to_eazyz(v):
 
 
 def log_map(R):
-    """Unbatched log map (reference test helper) — lie_tools.py:100-109."""
+    """Log map to skew matrices — lie_tools.py:100-109.
+
+    A single (3,3) matrix keeps the reference's tensor expression (a test helper there:
+    ``torch.trace`` makes it unbatched; NaN at the identity, no digits near π), on any device.
+    Input with leading dimensions, which the reference raises on, goes through the HIP kernel:
+    ``map_to_lie_algebra(so3_log(R))``, (...,3,3)."""
+    if R.dim() > 2:
+        return map_to_lie_algebra(so3_log(R))
     anti_sym = .5 * (R - R.transpose(-1, -2))
     theta = torch.acos(.5 * (torch.trace(R) - 1))
     return theta / torch.sin(theta) * anti_sym
+
+
+def so3_log(R):
+    """so(3) log, (...,3,3) rotations -> (...,3) with |v| ∈ [0, π]; the inverse of ``rodrigues``.
+
+    Stable over the whole range (the identity gives exactly 0; near π the axis comes from the
+    symmetric part of R) and differentiable with the tangent-space gradient R·hat(u)
+    (include/lievae.h).  At exactly π the axis' largest component is positive.  Extension:
+    the reference has only the unbatched ``log_map``."""
+    assert list(R.shape[-2:]) == [3, 3], 'Input must be 3x3 matrices'
+    return _ops.unary(R, _ops.SO3_LOG)
+
+
+def geodesic_distance(A, B):
+    """Rotation angle of AᵀB, (...,3,3) × (...,3,3) of one shape -> (...) in [0, π]: the
+    geodesic distance on SO(3).  Differentiable in both (gradient 0 where the distance is 0).
+    Extension."""
+    assert list(A.shape[-2:]) == [3, 3] and list(B.shape[-2:]) == [3, 3], \
+        'Input must be 3x3 matrices'
+    return _ops.so3_angle(A, B)
 
 
 def group_matrix_to_quaternions(r):

@@ -14,7 +14,8 @@ Same module names, constructor arguments, stateful attributes (``sigma``, ``z``,
 Extension (superset of the reference API): ``forward(x, n, eps=None)`` accepts an
 injected standard-normal ε of shape (n, B, z_dim), used by the parity tests; by
 default ε is drawn on the device with ``torch.randn`` as the reference's
-``Normal.sample`` does.  ``Sreparameterize`` names its injected normals ``noise``
+``Normal.sample`` does.  ``SO3reparameterize.log_prob(z)`` evaluates log q(z|x) at given
+rotations through the log-map kernel.  ``Sreparameterize`` names its injected normals ``noise``
 (n, B, 6·trials + 3).
 """
 import math
@@ -265,6 +266,18 @@ class SO3reparameterize(nn.Module):
         if v.dim() == 2:
             v = v.unsqueeze(0)
         return _ops.so3_log_posterior(v, sigma, self.k)
+
+    def log_prob(self, z):
+        """log q(z|x) at given rotations z, (n,B,3,3) or (B,3,3) -> (n,B), under the last
+        ``forward``'s ``mu_lie`` and σ: the wrapped density at v = log(μᵀz) (HIP kernels both).
+        Differentiable in z, in the mean head and in σ.  The density sums the sheets θ + 2πj,
+        so the branch of the log does not matter: ``log_prob(self.z)`` equals
+        ``log_posterior()`` also where the drawn |v| exceeded π.  Extension: the reference
+        evaluates the density only at its own sample."""
+        if z.dim() == 3:
+            z = z.unsqueeze(0)
+        v = _ops.so3_rel_log(self.mu_lie, z)
+        return _ops.so3_log_posterior(v, self.reparameterize.sigma, self.k)
 
     def log_prior(self):
         # torch.tensor([-log 8pi^2], device=...) (reparameterize.py:265-267) is float64 (torch
