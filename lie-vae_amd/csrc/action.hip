@@ -351,7 +351,11 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   a.Sw = Sw;
   a.write_through = (int64_t)a.n * a.MC * out_bytes <= kWriteThroughMaxBytes ? 1 : 0;
   if (kEnvWT >= 0) a.write_through = kEnvWT;
-  a.prio = kEnvPrio;
+  a.prio = (short)kEnvPrio;
+  // the chain's operand prefetch (fwd_tile_body): the product's one path; LV_TILE_PREFETCH=0
+  // (A/B) runs every degree at depth 0, the order the bitwise test compares against
+  static const int kEnvPrefetch = LV_KNOB("LV_TILE_PREFETCH", 1);
+  a.chain_fetch = (short)(kEnvPrefetch != 0);
   static const int kEnvSpread = LV_KNOB("LV_TILE_SPREAD", 0);  // A/B: prologue tasks over all waves
   a.task_spread = kEnvSpread;
   a.ang_order = (short)kEnvAngOrder;
@@ -911,6 +915,27 @@ int lv_ab_fwd_classes(int fused, int64_t F_batch_stride, int out_dtype, int64_t 
   info[3] = (int)offsetof(ActionArgs, nclass);
   info[4] = (int)offsetof(ActionArgs, class_map);
   info[5] = (int)offsetof(ActionArgs, seg_mask);
+  return LV_OK;
+}
+
+// Operand prefetch of the forward tile kernel's chain (A/B build, host only): info[0] tile
+// kernel (1) or grid-stride (0: no prefetch), [1] ActionArgs::chain_fetch (1 = the kernel's
+// compile-time depths, 0 = depth 0 everywhere: LV_TILE_PREFETCH=0), [2] byte offset of that
+// field in ActionArgs, [3] the kernel's VGPR ceiling (tile_vgpr_ceiling), [4 + l] the
+// compile-time depth of degree l = 0..L (chain_depth: 0 off, 1 half, 2 full); info holds
+// 4 + LV_MAX_DEGREE + 1 ints.
+int lv_ab_fwd_chain(int fused, int64_t F_batch_stride, int out_dtype, int64_t n, int L, int C,
+                    int cus, int* info) {
+  clear_error();
+  LV_CHECK_ARG(info, "null info");
+  LV_CHECK_ARG(n > 0, "n must be > 0 (got %lld)", (long long)n);
+  FwdLaunch p;
+  if (int e = plan_fwd(fused != 0, F_batch_stride, out_dtype, n, L, C, cus > 0 ? cus : device_cus(), p)) return e;
+  info[0] = p.tile ? 1 : 0;
+  info[1] = p.tile ? p.a.chain_fetch : 0;
+  info[2] = (int)offsetof(ActionArgs, chain_fetch);
+  info[3] = tile_vgpr_ceiling(L);
+  for (int l = 0; l <= LV_MAX_DEGREE; ++l) info[4 + l] = l <= L ? chain_depth(L, l) : -1;
   return LV_OK;
 }
 

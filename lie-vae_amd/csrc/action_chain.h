@@ -182,6 +182,77 @@ __device__ __forceinline__ void xrot_lds(const float* tj, const float (&x)[2 * l
   });
 }
 
+// xrot_lds in two halves, so that a J product can stand between the LDS reads and their use
+// (fwd_tile_body's operand prefetch).  xrot_fetch issues the reads of slot A's quads [Q0, Q1)
+// of the multiples (quad k holds f = 4k .. 4k + 3; f = 1 .. l only) into the caller's arrays;
+// xrot_apply is xrot_lds' product on those arrays: the same FMAs on the same values in the
+// same order, so bitwise equal to xrot_lds whenever the reads were issued.
+template <int l>
+constexpr int xrot_quads() { return (l + 4) / 4; }
+template <int l>
+struct XrotOps {
+  float c[l + 1], s[l + 1];  // [f], f = 1..l ([0], cos 0 = 1 and sin 0 = 0, is never read)
+};
+// dst[F .. F + N) = src[F .. F + N) in the widest aligned LDS reads (src 16-byte aligned at
+// F = 0).  Exactly the N values: a 16-byte read with lanes the product never uses (f = 0,
+// f > l) leaves dead registers, which the register allocator hands to the J product's
+// results -- and the write-after-write hazard then waits for the read in the middle of the
+// product that was to cover it.
+template <int F, int N>
+__device__ __forceinline__ void lds_span(const float* src, float* dst) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  if constexpr (N >= 4 && F % 4 == 0) {
+    const f4 v = *reinterpret_cast<const f4*>(src + F);
+    dst[F] = v[0]; dst[F + 1] = v[1]; dst[F + 2] = v[2]; dst[F + 3] = v[3];
+    lds_span<F + 4, N - 4>(src, dst);
+  } else if constexpr (N >= 2 && F % 2 == 0) {
+    const f2 v = *reinterpret_cast<const f2*>(src + F);
+    dst[F] = v[0]; dst[F + 1] = v[1];
+    lds_span<F + 2, N - 2>(src, dst);
+  } else if constexpr (N >= 1) {
+    dst[F] = src[F];
+    lds_span<F + 1, N - 1>(src, dst);
+  }
+}
+template <int l, int A, int LT, int Q0, int Q1>
+__device__ __forceinline__ void xrot_fetch(const float* tj, XrotOps<l>& t) {
+  constexpr int TP = TrigLds<LT>::TP;
+  static_assert(0 <= Q0 && Q0 <= Q1 && Q1 <= xrot_quads<l>(), "xrot_fetch: quad range");
+  constexpr int lo = 4 * Q0 > 1 ? 4 * Q0 : 1, hi = 4 * Q1 - 1 < l ? 4 * Q1 - 1 : l;  // f in [lo, hi]
+  if constexpr (hi >= lo) {
+    lds_span<lo, hi - lo + 1>(tj + 2 * A * TP, t.c);
+    lds_span<lo, hi - lo + 1>(tj + (2 * A + 1) * TP, t.s);
+  }
+}
+template <int l>
+__device__ __forceinline__ void xrot_apply(const XrotOps<l>& t, const float (&x)[2 * l + 1],
+                                           float (&y)[2 * l + 1]) {
+  sfor<2 * l + 1>([&](auto I) {
+    constexpr int i = LV_CV(I);
+    constexpr int f = l - i;
+    if constexpr (f == 0) {
+      y[i] = x[i];
+    } else if constexpr (f > 0) {
+      y[i] = fmaf(t.c[f], x[i], t.s[f] * x[2 * l - i]);
+    } else {
+      y[i] = fmaf(t.c[-f], x[i], -(t.s[-f] * x[2 * l - i]));
+    }
+  });
+}
+
+// A point in the instruction stream that a product's values pass through: empty asm
+// statements (no instruction is emitted) that take each value in and out of its VGPR and
+// clobber memory.  Arithmetic that produced the values stays above it, arithmetic that uses
+// them below, and no LDS access crosses it -- so reads issued above it are in flight while
+// the arithmetic below it runs.  (A sched_barrier does not do this: the FMAs carry no
+// ordering against it and the compiler gathers every read of a degree at its top.)
+template <int n>
+__device__ __forceinline__ void chain_pin(float (&v)[n]) {
+#pragma unroll
+  for (int i = 0; i < n; ++i) asm volatile("" : "+v"(v[i])::"memory");
+}
+
 // y = X_l(θ_A)^T x = X_l(-θ_A) x
 template <int l, int A, int LT>
 __device__ __forceinline__ void xrot_t(const TrigTab<LT>& t, const float (&x)[2 * l + 1],

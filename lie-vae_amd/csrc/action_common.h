@@ -28,8 +28,11 @@ struct alignas(64) ActionArgs {
   float* ang_out;       // optional (fused)
   int64_t n;
   int Sw;
-  int prio;             // tile kernel wave priority: 2 = prologue at s_setprio 3, chain at 0
+  short prio;           // tile kernel wave priority: 2 = prologue at s_setprio 3, chain at 0
                         // (default); A/B: 0 off, 1 flush at 3, 3 = 2 + flush at 2
+  short chain_fetch;    // tile kernel, A/B: 1 = the chain's operand prefetch at the kernel's
+                        // compile-time depths (chain_depth, action_fwd.h; the product's one
+                        // path), 0 = depth 0 at every degree: each LDS read right before its use
   short task_spread;    // tile kernel: prologue task t on lane t / nw of wave t % nw (1) instead
                         // of thread t (0: all tasks in wave 0)
   short nclass;         // tile kernel, A/B: block priority classes of the chain (0 = off, 2, 3):
@@ -62,6 +65,7 @@ struct alignas(64) ActionArgs {
 static_assert(offsetof(ActionArgs, seg_mask) == 64 && offsetof(ActionArgs, ang) == 128,
               "ActionArgs: the tile kernel's start-up fields fill the first two 64-byte lines");
 static_assert(offsetof(ActionArgs, nclass) < 64 && offsetof(ActionArgs, class_map) < 64 &&
+                  offsetof(ActionArgs, chain_fetch) < 64 &&
                   offsetof(ActionArgs, write_through) + sizeof(int) == 64,
               "ActionArgs: the block-class fields ride in line 0, in the start-up's one batch of loads");
 constexpr int kClassMapSlot = 0x40;   // ActionArgs::class_map: class from the workgroup's CU slot
@@ -71,8 +75,8 @@ constexpr int kMaxClasses = 3;        // chain priorities 2, 1, 0 under the prol
 
 // A/B build (-DLV_AB_KNOBS -> liblievae_hip_ab.so, its own instantiation objects): the
 // planner's environment knobs and, in the kernels, what only those knobs reach.  In the
-// product's tile kernel the fields below that no product plan varies (prio, task_spread,
-// ang_order, nclass, class_map, write_through 2) are compile-time constants -- the planner's
+// product's tile kernel the fields below that no product plan varies (prio, chain_fetch,
+// task_spread, ang_order, nclass, class_map, write_through 2) are compile-time constants -- the planner's
 // defaults -- so their branches, the second copy of the angle maths behind the prologue
 // barrier and the third copy of the flush are not in its code.
 //

@@ -264,6 +264,37 @@ __device__ __forceinline__ int tile_block_class(int nclass, int class_map) {
   return (int)(nclass == 2 ? (x & 1u) : x % 3u);
 }
 
+// Operand prefetch of the tile kernel's chain (fwd_tile_body `degree`): how many of the next
+// rotation's multiples a lane holds in registers across the J product in front of it.  A
+// fixed choice per kernel and degree, like kTilePrio, against the kernel's VGPR ceiling:
+//   * up to l_max = 10 the ceiling is 64, 8 waves per SIMD: the 8-wave plan (batch 16,384)
+//     runs 4 blocks per CU there and 3 from 65 VGPRs (16.8 -> 17.9 us measured with a build
+//     that held the reads' unused lanes, 65 VGPRs).  Every degree holds all 2l multiples:
+//     the compiler finishes one parity block of J_l before the other, so the held values
+//     fit beside the product -- the l_max = 10, C = 10, fp32 kernel compiles to 61 VGPRs
+//     against 62 at depth 0;
+//   * beyond, 104: the l = 20 bf16 kernel of config 5 needs every one of its 4 wave slots per
+//     SIMD and stood at 96-97.  There a degree's product has its 2(2l + 1) input and output
+//     values live and kChainRegsOther more (addresses, lane indices, temporaries: 82 + 14 at
+//     l = 20); full depth may add 2(l + 1), half depth the first (l + 4) / 8 quads of cos and
+//     sin.  Low degrees get the full depth for free: the top degree sets the register count.
+constexpr int kChainDepthOff = 0, kChainDepthHalf = 1, kChainDepthFull = 2;
+constexpr int kChainRegsOther = 16;
+constexpr int kChainFullMaxL = 10;
+constexpr int tile_vgpr_ceiling(int LT) { return LT <= kChainFullMaxL ? 64 : 104; }
+// depth of degree l in the kernel of l_max LT (compile-time in the kernel; the plan query
+// reports it)
+constexpr int chain_depth(int LT, int l) {
+  if (LT <= kChainFullMaxL) return kChainDepthFull;
+  const int ceiling = tile_vgpr_ceiling(LT);
+  const int live = 2 * (2 * l + 1) + kChainRegsOther;
+  if (live + 2 * (l + 1) <= ceiling) return kChainDepthFull;
+  if ((l + 4) / 8 > 0 && live + 8 * ((l + 4) / 8) <= ceiling) return kChainDepthHalf;
+  return kChainDepthOff;
+}
+static_assert(chain_depth(10, 10) == kChainDepthFull && chain_depth(20, 20) == kChainDepthOff,
+              "chain depth: config 2 prefetches its top degree, config 5's top degree has no room");
+
 // Tile kernel.  One block = one sample group (Sw = 64 / C samples, one wave's lanes) x
 // nseg degree segments, one wave per segment.
 //   1. Prologue ONCE per (sample j, Euler slot q): the block's first 3*Sw threads each
@@ -272,8 +303,8 @@ __device__ __forceinline__ int tile_block_class(int nclass, int class_map) {
 //      block's LDS table.  Every segment wave used to repeat the whole prologue on all
 //      its lanes: 5x the work at batch 4096 and ~40% of the kernel's VALU stream.
 //   2. Meanwhile each wave stages its spectrum slice; one barrier publishes both.
-//   3. Chain per degree with the multiples read from LDS right before each X product
-//      (16-byte reads; low register pressure, 74 VGPRs at l = 10).
+//   3. Chain per degree with the multiples read from LDS one rotation ahead, across the J
+//      product in front of their use (chain_depth above; 61 VGPRs at l = 10, C = 10).
 //   4. Outputs parked in the LDS tile; barrier; one contiguous flush.
 // CT: compile-time C (0 = run-time a.C).  With CT the spectrum slice is staged row-major
 // ([row][c], no index division, immediate-offset reads); without it column-major.
@@ -313,6 +344,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   const int transp = a.transpose, wthrough = a.write_through;
   const int ang_order = kAbKnobs ? a.ang_order : 0;
   const int nclass = kAbKnobs ? a.nclass : 0, class_map = kAbKnobs ? a.class_map : 0;
+  const int cfetch = kAbKnobs ? a.chain_fetch : 1;
   // this wave's degrees: a bit set (compile-time C: any set the planner balanced by cost);
   // run-time C keeps contiguous ranges [lo, hi) for its column-major spectrum slices
   const unsigned dmask = a.seg_mask[wave];
@@ -320,7 +352,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   if constexpr (kAbKnobs)
     asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(prio), "s"(spread),
                  "s"(transp), "s"(ang_order), "s"(wthrough), "s"(nclass), "s"(class_map), "s"(dmask),
-                 "s"(nthr));
+                 "s"(nthr), "s"(cfetch));
   else
     asm volatile("" ::"s"(vin), "s"(aF), "s"(aout), "s"(aang), "s"(an), "s"(Sw), "s"(transp),
                  "s"(wthrough), "s"(dmask), "s"(nthr));
@@ -536,28 +568,69 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   const float* Fl = FG ? aF + c : (CT > 0 ? Fall + c : Fw + c * frows - rows_lo);
   const int fstep = (FG || CT > 0) ? C : 1;  // stride between consecutive rows of a column
 
-  sfor<LT + 1>([&](auto Lc) {
-    constexpr int l = LV_CV(Lc);
-    if ((dmask >> l) & 1u) {
-      constexpr int nn = 2 * l + 1;
-      constexpr int r0 = l * l;
-      float x[nn], y[nn];
+  // One degree of the chain at operand-prefetch depth D (chain_depth).  Depth 0 reads every
+  // operand right before its use (xrot_lds): four exposed LDS round trips per degree on the
+  // wave's serial path.  From depth 1 the spectrum column and slot c's multiples leave as one
+  // batch behind one wait, and the multiples of the next rotation are issued BEFORE the J
+  // product that precedes it and consumed after it -- all of them (full) or their first
+  // (l + 4) / 8 quads (half, the rest at the point of use) -- so the product's ~2 nnz(J_l)
+  // FMAs cover the round trip.  The addresses are known at the prologue barrier and nothing
+  // the chain produces feeds them; the FMAs and their order are those of depth 0, so the
+  // outputs are bitwise the same.  chain_pin holds each J product between the issue of the
+  // reads and their use (left alone the compiler gathers a degree's reads at its top, at 96
+  // VGPRs, or sinks them to their use).
+  auto degree = [&](auto Lc, auto Dc) {
+    constexpr int l = LV_CV(Lc), D = LV_CV(Dc);
+    constexpr int nn = 2 * l + 1;
+    constexpr int r0 = l * l;
+    float x[nn], y[nn];
+    if constexpr (D == kChainDepthOff) {
       sfor<nn>([&](auto K) { x[LV_CV(K)] = Fl[(r0 + LV_CV(K)) * fstep]; });
       xrot_lds<l, 2, LT>(tj, x, y);
       jmul<l>(y, x);
       xrot_lds<l, 1, LT>(tj, x, y);
       jmul<l>(y, x);
       xrot_lds<l, 0, LT>(tj, x, y);
-      if (active) {
-        OutT* d = st_lane + r0 * C;
-        sfor<nn>([&](auto I) {
-          d[0] = tile_cvt(y[LV_CV(I)], (OutT*)nullptr);
-          d += C;
-        });
-      }
-      degree_stamp(a.stamps, wave, l);
+    } else {
+      constexpr int NQ = xrot_quads<l>();
+      constexpr int QH = D == kChainDepthFull ? NQ : (l + 4) / 8;  // quads fetched a stage ahead
+      XrotOps<l> ta, tb;
+      xrot_fetch<l, 2, LT, 0, NQ>(tj, ta);
+      sfor<nn>([&](auto K) { x[LV_CV(K)] = Fl[(r0 + LV_CV(K)) * fstep]; });
+      xrot_apply<l>(ta, x, y);
+      xrot_fetch<l, 1, LT, 0, QH>(tj, tb);  // in flight over the J product
+      chain_pin(y);
+      jmul<l>(y, x);
+      chain_pin(x);
+      xrot_fetch<l, 1, LT, QH, NQ>(tj, tb);
+      xrot_apply<l>(tb, x, y);
+      xrot_fetch<l, 0, LT, 0, QH>(tj, ta);
+      chain_pin(y);
+      jmul<l>(y, x);
+      chain_pin(x);
+      xrot_fetch<l, 0, LT, QH, NQ>(tj, ta);
+      xrot_apply<l>(ta, x, y);
     }
-  });
+    if (active) {
+      OutT* d = st_lane + r0 * C;
+      sfor<nn>([&](auto I) {
+        d[0] = tile_cvt(y[LV_CV(I)], (OutT*)nullptr);
+        d += C;
+      });
+    }
+    degree_stamp(a.stamps, wave, l);
+  };
+  // The product runs each degree at its compile-time depth; the A/B library also holds the
+  // chain at depth 0 (ActionArgs::chain_fetch 0, LV_TILE_PREFETCH=0), the order to compare with.
+  auto chain = [&](auto On) {
+    sfor<LT + 1>([&](auto Lc) {
+      constexpr int l = LV_CV(Lc);
+      constexpr int D = LV_CV(On) ? chain_depth(LT, l) : kChainDepthOff;
+      if ((dmask >> l) & 1u) degree(Lc, std::integral_constant<int, D>{});
+    });
+  };
+  if (kAbKnobs && !cfetch) chain(std::false_type{});
+  else chain(std::true_type{});
   phase_stamp(a.stamps, wave, 2);
   block_sync_lds();
   phase_stamp(a.stamps, wave, 3);

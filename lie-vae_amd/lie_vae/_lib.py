@@ -122,7 +122,8 @@ EXPORTED = sorted(list(_SIGS) + list(_SIGS_EXTRA))
 # entry points of the A/B build only (liblievae_hip_ab.so, -DLV_AB_KNOBS; tools/ sweeps):
 # bound when the loaded library has them, never part of the product header
 _SIGS_AB = {"lv_deconv4s2_fwd_bf16_tile": [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, _P],
-            "lv_ab_fwd_classes": [_I, _I64, _I, _I64, _I, _I, _I, _P]}
+            "lv_ab_fwd_classes": [_I, _I64, _I, _I64, _I, _I, _I, _P],
+            "lv_ab_fwd_chain": [_I, _I64, _I, _I64, _I, _I, _I, _P]}
 
 _lib = None
 
@@ -194,6 +195,18 @@ def fwd_classes(fused, F_batch_stride, out_dtype, n, L, C, cus=0):
     buf = (ctypes.c_int * 6)()
     call("lv_ab_fwd_classes", fused, F_batch_stride, out_dtype, n, L, C, cus, buf)
     return dict(zip(("tile", "nclass", "class_map", "off_nclass", "off_class_map", "off_seg_mask"), buf))
+
+
+def fwd_chain(fused, F_batch_stride, out_dtype, n, L, C, cus=0):
+    """Operand prefetch of the forward tile kernel's chain as a dict (A/B library only;
+    action.hip lv_ab_fwd_chain); no GPU call.  depths[l]: 0 off, 1 half, 2 full."""
+    if not hasattr(load(), "lv_ab_fwd_chain"):
+        raise LieVaeHipError("lv_ab_fwd_chain: an entry of the A/B library (liblievae_hip_ab.so)")
+    buf = (ctypes.c_int * 25)()
+    call("lv_ab_fwd_chain", fused, F_batch_stride, out_dtype, n, L, C, cus, buf)
+    d = dict(zip(("tile", "chain_fetch", "off_chain_fetch", "vgpr_ceiling"), buf[:4]))
+    d["depths"] = [x for x in buf[4:] if x >= 0]
+    return d
 
 
 def rotate_plan(N, C, H, W, flags=0):

@@ -101,6 +101,19 @@ def drain(st, s, t0, nblk, launch_us):
             if m.any():
                 print(f"    blocks on a CU with {k}: chain end p50/max {np.median(chain_end[m]):5.2f} {chain_end[m].max():5.2f}  "
                       f"flush end p50/max {np.median(fl1[m]):5.2f} {fl1[m].max():5.2f} us")
+        # the first-arrived block of each CU wins VALU issue by age: its chain is the path to
+        # the CU's first flush
+        first = np.zeros(nblk, dtype=bool)
+        for k in range(len(cnt)):
+            idx = np.nonzero(inv == k)[0]
+            first[idx[np.argmin(s[idx, 0, 0])]] = True
+        ch = us(s[first][:, :, 2] - s[first][:, :, 1])
+        print(f"  first-arrived block of each CU ({int(first.sum())}): prologue barrier -> chain end per wave, p50/p90: " +
+              "  ".join(f"w{w} {np.median(ch[:, w]):4.2f}/{np.percentile(ch[:, w], 90):4.2f}" for w in range(nwave)))
+        b2f = us(s[first][:, :, 3].max(axis=1) - s[first][:, :, 1].max(axis=1))
+        print(f"    its barrier -> flush start p10/50/90 {np.percentile(b2f, 10):5.2f} {np.median(b2f):5.2f} "
+              f"{np.percentile(b2f, 90):5.2f} us; its flush start from grid start p10/50/90 "
+              f"{np.percentile(fl0[first], 10):5.2f} {np.median(fl0[first]):5.2f} {np.percentile(fl0[first], 90):5.2f} us")
 
 
 def report(name, st, nblk, nwave, phases, red=None, nred=0, extra=None, launch_us=None):
