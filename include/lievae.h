@@ -163,6 +163,51 @@ int lv_so3_angle_fwd_f64(const double* A, const double* B, double* theta, int64_
 int lv_so3_angle_bwd_f64(const double* A, const double* B, const double* gtheta, double* gA,
                          double* gB, int64_t n, void* stream);
 
+/* ---- projection onto SO(3) (extension; not in the reference) -- csrc/so3_stats.hip -------
+ * R = argmin over rotations of |R - M|_F = U diag(1, 1, det UV^T) V^T for M = U diag(s) V^T:
+ * M (n,3,3) -> R (n,3,3).  With s3' = s3 det(UV^T) the map is well defined where
+ * s2 + s3' > 0; gamma = (s2 + s3')/s1 is the inverse of its condition number.  Computed by
+ * Davenport's q-method (the top eigenvector of a symmetric 4x4 by cyclic Jacobi sweeps), one
+ * thread per matrix.  For every finite M the output is a rotation (orthonormal to a few ulp,
+ * det > 0, no NaN); where the minimiser is not unique (gamma = 0: M = 0, rank 1, a
+ * reflection) the choice is deterministic, and M = 0 gives the identity.
+ * Backward: the output is a rotation, so the gradient is the tangent-space gradient
+ * gM = R hat(u) with (tr(P) I - P) u = vee(R^T gR - gR^T R), P = sym(R^T M).  Where
+ * gamma <= sqrt(eps) of the compute type (2^-12 in fp32, 2^-26 in fp64) the forward itself
+ * has lost half its digits: there the sample's gradient is exactly 0 (masked).
+ * Negative n, or a null pointer with work to do, return LV_ERR_ARG before any launch. */
+int lv_so3_project_fwd(const float* M, float* R, int64_t n, void* stream);
+int lv_so3_project_bwd(const float* M, const float* gR, float* gM, int64_t n, void* stream);
+int lv_so3_project_fwd_f64(const double* M, double* R, int64_t n, void* stream);
+int lv_so3_project_bwd_f64(const double* M, const double* gR, double* gM, int64_t n,
+                           void* stream);
+
+/* ---- rotation moment: the reduction behind the chordal mean and both Procrustes steps of
+ * pose alignment (extension) ----------------------------------------------------------------
+ *   S[s] = sum_i w_i op(X_i) C_s op(Y_i),  s < ns <= 8      S (ns,3,3) double
+ *   wsum = sum_i w_i                                          double (may be NULL)
+ *   R[s] = project(S[s]), projected in fp64                   (ns,3,3) of the input type (may
+ *                                                             be NULL)
+ * X, Y (n,3,3); Y NULL = identity; w (n) or NULL = ones; C (ns,3,3) in device memory or NULL =
+ * identity with ns = 1; flags: LV_MOMENT_XT / _YT / _CT transpose X_i / Y_i / C_s.  One pass
+ * reads X and Y once for all ns constants.  Two launches: partial sums whose grid depends on
+ * n alone (each thread adds its samples in ascending order in fp64, each block combines in a
+ * fixed order) into the caller's workspace of lv_so3_moment_workspace(n, ns) bytes, then one
+ * block that adds the partials in order.  No atomics: the same inputs give the same bits on
+ * every run and every device.  n = 0 writes S = 0, wsum = 0 and R = I.
+ * n < 0, ns outside [1, 8] (or ns > 1 without C), unknown flags, a null S, a null X with
+ * n > 0 or a short workspace return LV_ERR_ARG before any launch. */
+#define LV_MOMENT_XT 1
+#define LV_MOMENT_YT 2
+#define LV_MOMENT_CT 4
+size_t lv_so3_moment_workspace(int64_t n, int ns);
+int lv_so3_moment(const float* X, const float* Y, const float* w, const float* C, int ns,
+                  int flags, double* S, double* wsum, float* R, int64_t n, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int lv_so3_moment_f64(const double* X, const double* Y, const double* w, const double* C, int ns,
+                      int flags, double* S, double* wsum, double* R, int64_t n, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- s2s2_gram_schmidt, fp64: lie_tools.py:81-89 (S2S2Mean, reparameterize.py:184-197)
  * Crosses along the last axis (the reference's torch.cross without dim is
  * wrong at batch 3; documented deviation). */

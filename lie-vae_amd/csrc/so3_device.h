@@ -564,4 +564,160 @@ __device__ __forceinline__ void s2s2_bwd(const double v1[3], const double v2[3],
   for (int i = 0; i < 3; ++i) gv1[i] = (ge1[i] - (pass1 ? de1 * st.e1[i] : 0.0)) / st.n1c;
 }
 
+// ------------------------------------------------- projection onto SO(3) (extension)
+// R = argmin over rotations of |R - M|_F = U diag(1, 1, det UV^T) V^T, by Davenport's
+// q-method: tr(R(q)^T M) = q^T K q with the symmetric traceless
+//   K = [ M + M^T - tr(M) I   z ;  z^T   tr(M) ],  z = vee(M - M^T),  q = (x, y, z, w),
+// whose eigenvalues are {s1+s2+s3', s1-s2-s3', -s1+s2-s3', -s1-s2+s3'} (s3' = s3 det UV^T):
+// the top eigenvector is the quaternion of R, lam1 + lam2 = 2 s1 and lam1 - lam2 =
+// 2 (s2 + s3'), the gap that conditions the map.  K is diagonalised by a fixed number of
+// cyclic Jacobi sweeps, the six (p, q) pairs unrolled so that every entry of K and of the
+// eigenvector matrix has a compile-time index and lives in a register; the top column is
+// picked by selects.  M is first scaled by the power of two that brings its largest entry
+// into [1/2, 1) (exact), so every finite M is handled; ties of the largest eigenvalue go
+// to the scalar part first, so M = 0 gives the identity.
+template <typename T>
+__device__ __forceinline__ constexpr int project_sweeps() { return sizeof(T) == 8 ? 8 : 6; }
+// gamma = (s2 + s3')/s1 <= sqrt(eps): the forward has lost half its digits, the backward is masked
+template <typename T>
+__device__ __forceinline__ constexpr T project_mask() {
+  return sizeof(T) == 8 ? T(1.4901161193847656e-08) : T(2.44140625e-04);  // 2^-26, 2^-12
+}
+
+template <int P, int Q, typename T>
+__device__ __forceinline__ void jacobi_rotate(T (&a)[4][4], T (&v)[4][4]) {
+  // t = tan of the rotation angle, the smaller root of t^2 + 2 tau t - 1 = 0 with
+  // tau = d / b, written without forming tau: |b| / (|d| + sqrt(d^2 + b^2)), signed as d b.
+  // The denominator is >= |b|; holding it there keeps t finite where d = 0 and b^2 underflows
+  // (the last sweeps on a matrix with repeated eigenvalues, e.g. K of an exact rotation).
+  const T apq = a[P][Q];
+  const bool nz = apq != T(0.);
+  const T d = a[Q][Q] - a[P][P], b = T(2.) * apq;
+  T t = fabs(b) / fmax(fabs(d) + sqrt(d * d + b * b), fabs(b));
+  t = ((d >= T(0.)) == (b >= T(0.))) ? t : -t;
+  t = nz ? t : T(0.);
+  const T c = T(1.) / sqrt(T(1.) + t * t);
+  const T s = t * c;
+  const T h = t * apq;
+  a[P][P] = a[P][P] - h;
+  a[Q][Q] = a[Q][Q] + h;
+  a[P][Q] = a[Q][P] = T(0.);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (r != P && r != Q) {
+      const T arp = a[r][P], arq = a[r][Q];
+      a[r][P] = a[P][r] = c * arp - s * arq;
+      a[r][Q] = a[Q][r] = s * arp + c * arq;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const T vrp = v[r][P], vrq = v[r][Q];
+    v[r][P] = c * vrp - s * vrq;
+    v[r][Q] = s * vrp + c * vrq;
+  }
+}
+
+__device__ __forceinline__ float lv_ldexp(float x, int e) { return ldexpf(x, e); }
+__device__ __forceinline__ double lv_ldexp(double x, int e) { return ldexp(x, e); }
+__device__ __forceinline__ float lv_frexp(float x, int* e) { return frexpf(x, e); }
+__device__ __forceinline__ double lv_frexp(double x, int* e) { return frexp(x, e); }
+
+template <typename T>
+struct ProjectEig {
+  T lam1, lam2;  // the two largest eigenvalues of K (of the scaled M)
+};
+
+template <typename T>
+__device__ __forceinline__ void so3_project(const T M[9], T R[9], ProjectEig<T>& pe) {
+  T mx = fabs(M[0]);
+#pragma unroll
+  for (int k = 1; k < 9; ++k) mx = fmax(mx, fabs(M[k]));
+  int e;
+  (void)lv_frexp(mx, &e);
+  T m[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m[k] = lv_ldexp(M[k], -e);
+  const T tr = (m[0] + m[4]) + m[8];
+  T a[4][4], v[4][4];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      a[i][j] = i == j ? (m[i * 3 + j] + m[j * 3 + i]) - tr : m[i * 3 + j] + m[j * 3 + i];
+  a[0][3] = a[3][0] = m[7] - m[5];
+  a[1][3] = a[3][1] = m[2] - m[6];
+  a[2][3] = a[3][2] = m[3] - m[1];
+  a[3][3] = tr;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[r][k] = r == k ? T(1.) : T(0.);
+#pragma unroll 1
+  for (int sweep = 0; sweep < project_sweeps<T>(); ++sweep) {
+    // round-robin order: the two rotations of a line touch disjoint rows and columns, so
+    // the second one's angle does not wait for the first (two chains in flight per thread)
+    jacobi_rotate<0, 1>(a, v);
+    jacobi_rotate<2, 3>(a, v);
+    jacobi_rotate<0, 2>(a, v);
+    jacobi_rotate<1, 3>(a, v);
+    jacobi_rotate<0, 3>(a, v);
+    jacobi_rotate<1, 2>(a, v);
+  }
+  const T d0 = a[0][0], d1 = a[1][1], d2 = a[2][2], d3 = a[3][3];
+  int k = 3;
+  T best = d3;
+  if (d0 > best) { best = d0; k = 0; }
+  if (d1 > best) { best = d1; k = 1; }
+  if (d2 > best) { best = d2; k = 2; }
+  const T q0 = sel4(k, v[0][0], v[0][1], v[0][2], v[0][3]);
+  const T q1 = sel4(k, v[1][0], v[1][1], v[1][2], v[1][3]);
+  const T q2 = sel4(k, v[2][0], v[2][1], v[2][2], v[2][3]);
+  const T q3 = sel4(k, v[3][0], v[3][1], v[3][2], v[3][3]);
+  pe.lam1 = best;
+  pe.lam2 = fmax(fmax(fmin(d0, d1), fmin(d2, d3)), fmin(fmax(d0, d1), fmax(d2, d3)));
+  const T nrm = sqrt((q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3));
+  const T x = q0 / nrm, y = q1 / nrm, z = q2 / nrm, w = q3 / nrm;
+  R[0] = ((w * w + x * x) - y * y) - z * z;
+  R[1] = T(2.) * (x * y - w * z);
+  R[2] = T(2.) * (x * z + w * y);
+  R[3] = T(2.) * (x * y + w * z);
+  R[4] = ((w * w - x * x) + y * y) - z * z;
+  R[5] = T(2.) * (y * z - w * x);
+  R[6] = T(2.) * (x * z - w * y);
+  R[7] = T(2.) * (y * z + w * x);
+  R[8] = ((w * w - x * x) - y * y) + z * z;
+}
+
+// Backward of the projection: the output is a rotation, so the gradient is the tangent-space
+// gradient gM = R hat(u) with (tr(P) I - P) u = vee(R^T gR - gR^T R), P = sym(R^T M), the
+// symmetric factor of the polar decomposition (eigenvalues of the system: s_i + s_j with s3'
+// signed; neither U nor V is needed).  Solved by cofactors.  Where gamma <= sqrt(eps) the
+// sample's gradient is exactly 0.
+template <typename T>
+__device__ __forceinline__ void so3_project_vjp(const T M[9], const T gR[9], T gM[9]) {
+  T R[9], Q[9], G[9];
+  ProjectEig<T> pe;
+  so3_project(M, R, pe);
+  const bool keep = (pe.lam1 - pe.lam2) > project_mask<T>() * (pe.lam1 + pe.lam2);
+  matmul3_tn(R, M, Q);
+  const T p00 = T(0.5) * (Q[0] + Q[0]), p11 = T(0.5) * (Q[4] + Q[4]), p22 = T(0.5) * (Q[8] + Q[8]);
+  const T p01 = T(0.5) * (Q[1] + Q[3]), p02 = T(0.5) * (Q[2] + Q[6]), p12 = T(0.5) * (Q[5] + Q[7]);
+  const T tr = (p00 + p11) + p22;
+  const T a = tr - p00, b = -p01, c = -p02, d = tr - p11, e = -p12, f = tr - p22;
+  const T c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
+  const T c11 = a * f - c * c, c12 = b * c - a * e, c22 = a * d - b * b;
+  T det = (a * c00 + b * c01) + c * c02;
+  det = keep ? det : T(1.);
+  matmul3_tn(R, gR, G);
+  const T r0 = G[7] - G[5], r1 = G[2] - G[6], r2 = G[3] - G[1];
+  T u[3];
+  u[0] = ((c00 * r0 + c01 * r1) + c02 * r2) / det;
+  u[1] = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
+  u[2] = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
+  mul_hat(R, u, gM);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) gM[k] = keep ? gM[k] : T(0.);
+}
+
 }  // namespace lv

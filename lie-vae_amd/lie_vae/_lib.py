@@ -66,6 +66,9 @@ _SIGS = {
     "lv_so3_rel_log_bwd": [_P, _P, _P, _P, _P, _I64, _I64, _P],
     "lv_so3_angle_fwd": [_P, _P, _P, _I64, _P],
     "lv_so3_angle_bwd": [_P, _P, _P, _P, _P, _I64, _P],
+    "lv_so3_project_fwd": [_P, _P, _I64, _P],
+    "lv_so3_project_bwd": [_P, _P, _P, _I64, _P],
+    "lv_so3_moment": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I64, _P, _SZ, _P],
 }
 # fp64 twins of the per-sample maps (same argument lists, double pointers)
 for _name in ("lv_so3_exp_fwd", "lv_so3_exp_bwd", "lv_so3_sample_fwd", "lv_so3_sample_bwd",
@@ -73,7 +76,8 @@ for _name in ("lv_so3_exp_fwd", "lv_so3_exp_bwd", "lv_so3_sample_fwd", "lv_so3_s
               "lv_mat_to_quat_fwd", "lv_mat_to_quat_bwd", "lv_quat_to_eazyz_fwd",
               "lv_quat_to_eazyz_bwd", "lv_mat_to_eazyz_fwd", "lv_mat_to_eazyz_bwd",
               "lv_s2s1_fwd", "lv_s2s1_bwd", "lv_so3_log_fwd", "lv_so3_log_bwd",
-              "lv_so3_rel_log_fwd", "lv_so3_rel_log_bwd", "lv_so3_angle_fwd", "lv_so3_angle_bwd"):
+              "lv_so3_rel_log_fwd", "lv_so3_rel_log_bwd", "lv_so3_angle_fwd", "lv_so3_angle_bwd",
+              "lv_so3_project_fwd", "lv_so3_project_bwd", "lv_so3_moment"):
     _SIGS[_name + "_f64"] = _SIGS[_name]
 _SIGS["lv_deconv4s2_pack_weight_bf16"] = [_P, _P, _I, _I, _P]
 _SIGS["lv_deconv4s2_fwd_bf16"] = [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _P]
@@ -98,6 +102,7 @@ _SIGS["lv_equivariance_diff_bwd"] = [_P, _P, _P, _P, _P, _P, _I64, _P]
 _SIGS["lv_pair_sqdist_fwd"] = [_P, _P, _I64, _I, _P]
 _SIGS["lv_pair_sqdist_bwd"] = [_P, _P, _P, _I64, _I, _P]
 LV_ROTATE_DIRECT = 1  # include/lievae.h
+LV_MOMENT_XT, LV_MOMENT_YT, LV_MOMENT_CT = 1, 2, 4  # include/lievae.h
 # vMF latent on S^3 (csrc/vmf.hip)
 _SIGS["lv_vmf_sample_fwd"] = [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]
 _SIGS["lv_vmf_sample_bwd"] = [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _P]
@@ -106,11 +111,13 @@ _SIGS["lv_vmf_kl_bwd"] = [_P, _P, _P, _I64, _P]
 _SIGS["lv_vmf_log_prob_fwd"] = [_P, _P, _P, _P, _I64, _I64, _P]
 _SIGS["lv_vmf_log_prob_bwd"] = [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]
 _RESTYPES = {"lv_group_action_bwd_workspace": _SZ, "lv_last_error": ctypes.c_char_p,
+             "lv_so3_moment_workspace": _SZ,
              "lv_deconv4s2_packed_weight_elems": _SZ, "lv_deconv4s2_small_packed_weight_elems": _SZ,
              "lv_deconv4s2_packed_weight_elems_f32": _SZ,
              "lv_deconv4s2_small_dgrad_weight_elems": _SZ, "lv_deconv4s2_small_bwd_workspace_elems": _SZ,
              "lv_channel_sum_workspace_elems": _SZ, "lv_bn_workspace_elems": _SZ}
-_SIGS_EXTRA = {"lv_group_action_bwd_workspace": [_I64, _I, _I, _I], "lv_last_error": [],
+_SIGS_EXTRA = {"lv_group_action_bwd_workspace": [_I64, _I, _I, _I],
+               "lv_so3_moment_workspace": [_I64, _I], "lv_last_error": [],
                "lv_deconv4s2_packed_weight_elems": [_I], "lv_deconv4s2_small_packed_weight_elems": [_I],
                "lv_deconv4s2_packed_weight_elems_f32": [_I],
                "lv_deconv4s2_small_dgrad_weight_elems": [_I],

@@ -76,9 +76,10 @@ QUAT_TO_EAZYZ = ("lv_quat_to_eazyz_fwd", "lv_quat_to_eazyz_bwd", (4,), (3,))
 MAT_TO_EAZYZ = ("lv_mat_to_eazyz_fwd", "lv_mat_to_eazyz_bwd", (3, 3), (3,))
 SOFTPLUS = ("lv_softplus_fwd", "lv_softplus_bwd", (), ())
 SO3_LOG = ("lv_so3_log_fwd", "lv_so3_log_bwd", (3, 3), (3,))
+SO3_PROJECT = ("lv_so3_project_fwd", "lv_so3_project_bwd", (3, 3), (3, 3))
 # maps with fp64 twins
 _F64_MAPS = {s[0] for s in (SO3_EXP, QUAT_TO_MAT, MAT_TO_QUAT, QUAT_TO_EAZYZ, MAT_TO_EAZYZ,
-                            SO3_LOG)}
+                            SO3_LOG, SO3_PROJECT)}
 
 
 def unary(x, spec):
@@ -225,6 +226,94 @@ def so3_angle(A, B):
         f"so3_angle: A and B must be (...,3,3) of one shape, got {tuple(A.shape)} and {tuple(B.shape)}"
     _lib.require_device(A, B)
     return _SO3Angle.apply(A, B)
+
+
+# ------------------------------------------------- rotation moment, mean, alignment
+MOMENT_MAX_NS = 8  # csrc/so3_stats.hip kMomentMaxNs
+
+
+def so3_moment(X, Y=None, weights=None, C=None, flags=0, project=True):
+    """S[s] = sum_i w_i op(X_i) C_s op(Y_i) (include/lievae.h lv_so3_moment): X, Y (n,3,3), weights
+    (n) or None, C (ns,3,3) or None (the identity, ns = 1), flags of _lib.LV_MOMENT_XT / _YT /
+    _CT.  Returns S (ns,3,3) fp64, wsum () fp64 and R (ns,3,3) = project(S) in the inputs'
+    dtype (None with project=False).  Two launches on the current stream, no host sync, bitwise
+    reproducible.  Forward only: inputs that require grad are refused."""
+    assert X.dim() == 3 and tuple(X.shape[1:]) == (3, 3), \
+        f"so3_moment: X must be (n,3,3), got {tuple(X.shape)}"
+    n = X.shape[0]
+    assert Y is None or tuple(Y.shape) == (n, 3, 3), \
+        f"so3_moment: Y must be ({n},3,3), got {tuple(Y.shape)}"
+    assert weights is None or tuple(weights.shape) == (n,), \
+        f"so3_moment: weights must be ({n},), got {tuple(weights.shape)}"
+    ns = 1 if C is None else C.shape[0]
+    assert C is None or (C.dim() == 3 and tuple(C.shape[1:]) == (3, 3)
+                         and 1 <= ns <= MOMENT_MAX_NS), \
+        f"so3_moment: C must be (ns,3,3) with 1 <= ns <= {MOMENT_MAX_NS}, got {tuple(C.shape)}"
+    _lib.require_device(X, Y, weights, C)
+    if any(t is not None and t.requires_grad for t in (X, Y, weights, C)):
+        raise RuntimeError("so3_moment (so3_mean, align_rotations) has no backward; detach the "
+                           "inputs")
+    dt = _map_dtype(X, Y, weights, C)
+    X, Y, weights, C = (None if t is None else _prep(t, dt) for t in (X, Y, weights, C))
+    dev = X.device
+    S = torch.empty((ns, 3, 3), device=dev, dtype=F64)
+    wsum = torch.empty((), device=dev, dtype=F64)
+    R = torch.empty((ns, 3, 3), device=dev, dtype=dt) if project else None
+    nb = int(_lib.load().lv_so3_moment_workspace(n, ns))
+    ws = torch.empty(max(nb, 8), device=dev, dtype=torch.uint8)
+    call(_k("lv_so3_moment", dt), ptr(X), ptr(Y), ptr(weights), ptr(C), ns, flags, ptr(S),
+         ptr(wsum), ptr(R), n, ptr(ws), nb, _lib.stream_of(dev))
+    return S, wsum, R
+
+
+def so3_mean(R, weights=None):
+    """Chordal mean of rotations: (n,3,3) -> (3,3), the projection of sum_i w_i R_i."""
+    return so3_moment(R, weights=weights)[2][0]
+
+
+def _half_turn_starts(device, dtype):
+    """The identity and the half-turns about x, y, z, (4,3,3); built by device kernels only
+    (no host-to-device copy, so it can be captured in a graph)."""
+    s = torch.arange(4, device=device)[:, None]
+    j = torch.arange(3, device=device)[None, :]
+    return torch.diag_embed(((s == 0) | (s == j + 1)).to(dtype) * 2 - 1)
+
+
+def align_rotations(Z, G, side='both', weights=None, rounds=16):
+    """(A, B, rms) minimising sum_i w_i |Z_i - A G_i B|_F^2 over rotations; Z, G (n,3,3).
+    'left' fixes B = I and 'right' fixes A = I: one closed-form Procrustes step each (one
+    lv_so3_moment).  'both' alternates the two steps `rounds` times from four starts of B --
+    the identity and the half-turns about x, y, z, carried as ns = 4 through the same launches
+    -- and keeps the start of lowest residual, selected on the device.  rms =
+    sqrt(residual / sum w), from the last moment: residual = 6 wsum - 2 tr(B^T S) (a difference:
+    an exact fit reads as ~sqrt(eps) of the rotations' dtype, not 0).  No host sync: capturable
+    in a graph.  Forward only."""
+    assert side in ('both', 'left', 'right'), f"align_rotations: side {side!r}"
+    assert Z.dim() == 3 and tuple(Z.shape[1:]) == (3, 3) and G.shape == Z.shape, \
+        f"align_rotations: Z and G must be (n,3,3) of one shape, got {tuple(Z.shape)} and " \
+        f"{tuple(G.shape)}"
+    _lib.require_device(Z, G, weights)
+    dt = _map_dtype(Z, G, weights)
+    XT, YT, CT = _lib.LV_MOMENT_XT, _lib.LV_MOMENT_YT, _lib.LV_MOMENT_CT
+    if side != 'both':
+        if side == 'left':
+            S, wsum, R = so3_moment(Z, G, weights, None, YT)
+        else:
+            S, wsum, R = so3_moment(G, Z, weights, None, XT)
+        eye = torch.eye(3, device=Z.device, dtype=dt)
+        res = 6 * wsum - 2 * (R[0].double() * S[0]).sum()
+        rms = torch.sqrt(res.clamp(min=0) / wsum).to(dt)
+        return (R[0], eye, rms) if side == 'left' else (eye, R[0], rms)
+    assert rounds >= 1, "align_rotations: rounds must be >= 1"
+    Bs = _half_turn_starts(Z.device, dt)
+    for _ in range(rounds):
+        As = so3_moment(Z, G, weights, Bs, YT | CT)[2]
+        S, wsum, Bs = so3_moment(G, Z, weights, As, XT | CT)
+    res = 6 * wsum - 2 * (Bs.double() * S).sum((-1, -2))
+    k = torch.argmin(res).reshape(1)
+    A, B = As.index_select(0, k)[0], Bs.index_select(0, k)[0]
+    rms = torch.sqrt(res.index_select(0, k)[0].clamp(min=0) / wsum).to(dt)
+    return A, B, rms
 
 
 class _N0Sample(torch.autograd.Function):

@@ -14,11 +14,13 @@ import torch.nn as nn
 from ..decoders import ActionNet, MLPNet
 from ..lie_tools import group_matrix_to_eazyz, quaternions_to_eazyz, vector_to_eazyz
 from ..reparameterize import (AlgebraMean, N0reparameterize, Nreparameterize, QuaternionMean,
-                              S2S1Mean, S2S2Mean, SO3reparameterize, Sreparameterize)
+                              S2S1Mean, S2S2Mean, SO3reparameterize, Sreparameterize, SVDMean)
 from ..utils import logsumexp
 from .nets import MLP, ConvNet, ConvNetBN, DeconvNet, Flatten
 
-_MEANS = {'alg': AlgebraMean, 'q': QuaternionMean, 's2s1': S2S1Mean, 's2s2': S2S2Mean}
+# 'svd' is an extension: a 9-D linear head projected onto SO(3)
+_MEANS = {'alg': AlgebraMean, 'q': QuaternionMean, 's2s1': S2S1Mean, 's2s2': S2S2Mean,
+          'svd': SVDMean}
 
 # Under reduced-precision autocast, the latent heads -- the encoder's last (4x4 -> 1x1)
 # GEMM conv and the mean / sigma linears (reparameterize.py:148-197) -- compute in fp32:

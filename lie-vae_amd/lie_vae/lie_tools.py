@@ -20,7 +20,8 @@ __all__ = [
     "s2s2_gram_schmidt", "vector_to_eazyz", "log_map", "group_matrix_to_quaternions",
     "quaternions_to_eazyz", "group_matrix_to_eazyz", "quaternions_to_group_matrix",
     "wigner_d_matrix", "block_wigner_matrix_multiply", "random_quaternions",
-    "random_group_matrices", "so3_log", "geodesic_distance",
+    "random_group_matrices", "so3_log", "geodesic_distance", "project_to_so3", "so3_mean",
+    "align_rotations",
 ]
 
 
@@ -98,6 +99,35 @@ def geodesic_distance(A, B):
     assert list(A.shape[-2:]) == [3, 3] and list(B.shape[-2:]) == [3, 3], \
         'Input must be 3x3 matrices'
     return _ops.so3_angle(A, B)
+
+
+def project_to_so3(M):
+    """Nearest rotation in the Frobenius norm, (...,3,3) -> (...,3,3): the orthogonal Procrustes
+    projection U·diag(1, 1, det UVᵀ)·Vᵀ of M = U·diag(s)·Vᵀ, in one kernel (Davenport's q-method;
+    include/lievae.h lv_so3_project_fwd) without forming U or V.  fp32 or fp64 following the
+    input.  Differentiable with the tangent-space gradient R·hat(u); where the gap
+    (s2 + s3')/s1 is below √eps the sample's gradient is exactly 0.  Every finite M gives a
+    rotation.  Extension: not in the reference."""
+    assert list(M.shape[-2:]) == [3, 3], 'Input must be 3x3 matrices'
+    return _ops.unary(M, _ops.SO3_PROJECT)
+
+
+def so3_mean(R, weights=None):
+    """Chordal (projected arithmetic) mean of rotations, (n,3,3) [, weights (n)] -> (3,3): a
+    deterministic fp64 reduction and its projection (lv_so3_moment).  Forward only.
+    Extension."""
+    assert R.dim() == 3 and list(R.shape[-2:]) == [3, 3], 'Input must be (n,3,3)'
+    return _ops.so3_mean(R, weights)
+
+
+def align_rotations(Z, G, side='both', weights=None, rounds=16):
+    """Rotations (A, B) and the rms residual with A·G_i·B ≈ Z_i in the least-squares (chordal)
+    sense; Z, G (n,3,3).  ``side='left'`` fixes B = I, ``'right'`` fixes A = I (closed-form
+    Procrustes steps); ``'both'`` alternates them ``rounds`` times from four starts of B (the
+    identity and the three coordinate half-turns: one is always within 120° of the optimum)
+    and keeps the best.  No host synchronisation; forward only.  Extension: the latent of an
+    action-decoder VAE is identified only up to such a pair."""
+    return _ops.align_rotations(Z, G, side=side, weights=weights, rounds=rounds)
 
 
 def group_matrix_to_quaternions(r):

@@ -8,7 +8,8 @@ Same module names, constructor arguments, stateful attributes (``sigma``, ``z``,
 * softplus σ and v = ε·σ                 (N0reparameterize, :100-145)
 * z = μ·exp(v)                            (SO3reparameterize.nsample, :269-273)
 * 21-term wrapped log-density + logsumexp (SO3reparameterize.log_posterior, :233-263)
-* mean maps rodrigues / quaternion / S2S1 / fp64 S2S2 (:148-197)
+* mean maps rodrigues / quaternion / S2S1 / fp64 S2S2 (:148-197), and the SVD head
+  (``SVDMean``, an extension)
 * the vMF latent on S³: rejection sampler, KL, log-density (Sreparameterize, :58-97)
 
 Extension (superset of the reference API): ``forward(x, n, eps=None)`` accepts an
@@ -27,8 +28,8 @@ import torch.nn.functional as F
 from torch.distributions import Normal
 
 from . import _ops
-from .lie_tools import (quaternions_to_group_matrix, rodrigues, s2s1rodrigues,
-                        s2s2_gram_schmidt)
+from .lie_tools import (project_to_so3, quaternions_to_group_matrix, rodrigues,
+                        s2s1rodrigues, s2s2_gram_schmidt)
 
 
 class Nreparameterize(nn.Module):
@@ -231,6 +232,20 @@ class S2S2Mean(nn.Module):
     def forward(self, x):
         v = self.map(x).double().view(-1, 2, 3)
         return s2s2_gram_schmidt(v[:, 0], v[:, 1]).float()
+
+
+class SVDMean(nn.Module):
+    """R^9 -> SO(3) by the orthogonal Procrustes projection of a linear 3x3 head (the "SVD"
+    parametrisation, the least-squares-optimal continuous one).  Extension: not in the
+    reference, whose mean maps are the four above; symmetric in the nine outputs, unlike
+    the Gram–Schmidt order of S2S2Mean."""
+
+    def __init__(self, input_dims):
+        super().__init__()
+        self.map = nn.Linear(input_dims, 9)
+
+    def forward(self, x):
+        return project_to_so3(self.map(x).reshape(-1, 3, 3))
 
 
 class SO3reparameterize(nn.Module):
