@@ -483,6 +483,32 @@ int lv_pair_sqdist_fwd(const float* enc, float* diffs, int64_t rows, int D, void
 int lv_pair_sqdist_bwd(const float* enc, const float* gdiffs, float* g_enc, int64_t rows, int D,
                        void* stream);
 
+/* ---- sphere-cube renderer (csrc/render.hip) ----------------------------------------------
+ * The images the reference's SphereCubeDataset / ScPairsDataset read from disk
+ * (experiments/datasets.py:87-127, rendered there by Blender from cube.blend), rendered on the
+ * device from the poses instead.  The scene is this project's own: the
+ * cube [-1,1]^3 with one albedo per face and a sphere of radius 0.6 at (0,0,1) in a fixed
+ * object frame, Lambert + ambient light from (1,2,3)/sqrt(14); the pose is the CAMERA frame
+ * (position 5 R[:,2], looking along -z of R, +y of R up, half-width 0.4 at unit distance).
+ * R (n,3,3) -> out (n, channels, size, size) fp32 in [0, 1], channels 3 (RGB) or 1 (the mean
+ * of the three); a pixel is the mean of samples x samples regular sub-samples.  One launch:
+ * a thread traces a run of 4 consecutive pixels (size % 4 == 0 and a 16-byte aligned out;
+ * float4 stores) or 1 pixel (otherwise, or with LV_RENDER_SCALAR) once and writes every
+ * channel from that trace; both give the same bits.  Forward only.  Every R, finite or not,
+ * gives a finite image and no fault: no address depends on a computed value.
+ * n < 0, size outside 1..1024, channels not 1 or 3, samples outside 1..4, unknown flags, a
+ * null pointer with n > 0, or n * channels * size^2 * 4 beyond INT64_MAX return LV_ERR_ARG
+ * before any launch. */
+#define LV_RENDER_SCALAR 1
+int lv_render_spherecube_fwd(const float* R, float* out, int64_t n, int size, int channels,
+                             int samples, int flags, void* stream);
+/* Host-only dispatch of the call above (for an aligned out): plan[0] four-pixel path (1) or
+ * one-pixel (0), [1] grid blocks = min(65536, n * ceil(runs / 256)) with runs = size^2 / 4 or
+ * size^2 per image (blocks stride over the rest), [2] threads per block, [3] dynamic LDS bytes
+ * per block. */
+#define LV_RENDER_PLAN_LEN 4
+int lv_render_plan(int64_t n, int size, int channels, int samples, int flags, int64_t* plan);
+
 #ifdef __cplusplus
 }
 #endif

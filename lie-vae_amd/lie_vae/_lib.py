@@ -102,6 +102,10 @@ _SIGS["lv_equivariance_diff_bwd"] = [_P, _P, _P, _P, _P, _P, _I64, _P]
 _SIGS["lv_pair_sqdist_fwd"] = [_P, _P, _I64, _I, _P]
 _SIGS["lv_pair_sqdist_bwd"] = [_P, _P, _P, _I64, _I, _P]
 LV_ROTATE_DIRECT = 1  # include/lievae.h
+# sphere-cube renderer (csrc/render.hip)
+_SIGS["lv_render_spherecube_fwd"] = [_P, _P, _I64, _I, _I, _I, _I, _P]
+_SIGS["lv_render_plan"] = [_I64, _I, _I, _I, _I, _P]
+LV_RENDER_SCALAR = 1  # include/lievae.h
 LV_MOMENT_XT, LV_MOMENT_YT, LV_MOMENT_CT = 1, 2, 4  # include/lievae.h
 # vMF latent on S^3 (csrc/vmf.hip)
 _SIGS["lv_vmf_sample_fwd"] = [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]
@@ -222,6 +226,14 @@ def rotate_plan(N, C, H, W, flags=0):
     buf = (ctypes.c_int64 * 4)()
     call("lv_rotate_plan", N, C, H, W, flags, buf)
     return dict(zip(("staged", "blocks", "threads", "lds_bytes"), buf))
+
+
+def render_plan(n, size, channels, samples, flags=0):
+    """Host-only dispatch of lv_render_spherecube_fwd as a dict; no GPU call
+    (include/lievae.h LV_RENDER_PLAN_LEN)."""
+    buf = (ctypes.c_int64 * 4)()
+    call("lv_render_plan", n, size, channels, samples, flags, buf)
+    return dict(zip(("wide", "blocks", "threads", "lds_bytes"), buf))
 
 
 TORCH_OPS_PATH =os.environ.get("LIEVAE_TORCH_OPS_LIB", os.path.join(_HERE, "liblievae_torch.so"))

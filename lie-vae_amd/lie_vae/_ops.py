@@ -718,6 +718,27 @@ def rotate_images(img, cs, align_corners=False, flags=0):
     return out
 
 
+# ------------------------------------------------------ sphere-cube renderer
+def render_spherecube(g, size=64, rgb=True, samples=2, flags=0):
+    """Images of the sphere-cube scene seen from the poses g (csrc/render.hip; the data the
+    reference's SphereCubeDataset reads from disk): g (n,3,3) camera frames, or (n,4)
+    scalar-last quaternions (through quaternions_to_group_matrix) -> (n, 3 | 1, size, size)
+    fp32 in [0, 1] on g's device, each pixel the mean of samples x samples sub-samples.  One
+    launch, no host sync; forward only (no gradient reaches g).  flags:
+    _lib.LV_RENDER_SCALAR forces the one-pixel path (same bits)."""
+    quats = g.dim() == 2 and g.shape[1] == 4
+    assert quats or (g.dim() == 3 and tuple(g.shape[1:]) == (3, 3)), \
+        f"g must be matrices (n,3,3) or quaternions (n,4), got {tuple(g.shape)}"
+    _lib.require_device(g)
+    g = g.detach()
+    R = _f32c(unary(g, QUAT_TO_MAT) if quats else g)
+    n, C = R.shape[0], 3 if rgb else 1
+    out = torch.empty((n, C, size, size), device=R.device, dtype=F32)
+    call("lv_render_spherecube_fwd", ptr(R), ptr(out), n, size, C, samples, flags,
+         _lib.stream_of(R.device))
+    return out
+
+
 class _EquivarianceDiff(torch.autograd.Function):
     """diffs[n] = sum (g_n enc_n - enc_rot_n)^2, g = s2s1rodrigues(e_x, cs) --
     losses/equivariance_loss.py:28-36.  cs carries no gradient (theta is drawn)."""

@@ -1,16 +1,26 @@
-"""Toy spectrum dataset (reference lie_vae/experiments/datasets.py:129-162, ``ToyDataset``).
+"""Datasets of the reference's lie_vae/experiments/datasets.py that the kernels can produce.
 
-The one dataset of the reference that is *produced* by the hot path: Haar-random poses q,
-one shared random spectrum scaled to Frobenius norm 10, and targets
-x = block_wigner_matrix_multiply(quaternions_to_eazyz(q), spectrum, degrees).  Both maps
-run in liblievae_hip.so, so ``generate`` needs a GPU device (the product path has no CPU
-fallback).  The on-disk image datasets (spherecube / ShapeNet readers) are out of scope
-(DESIGN.md §7): their files are absent and they never touch the SO(3) kernels.
+``ToyDataset`` (datasets.py:129-162): Haar-random poses q, one shared random spectrum scaled
+to Frobenius norm 10, and targets
+x = block_wigner_matrix_multiply(quaternions_to_eazyz(q), spectrum, degrees).
+
+``SphereCubeDataset`` / ``ScPairsDataset`` (datasets.py:87-127): the reference reads PNGs that
+Blender rendered from cube.blend; here the images come from the project's own sphere-cube
+scene (csrc/render.hip), rendered on the device from the poses, with the
+reference's item layout ``(name, group_el, image)``.  ``spherecube_batch`` renders a fresh
+batch per training step.
+
+All maps run in liblievae_hip.so, so every ``generate`` needs a GPU device (the product path
+has no CPU fallback).  Reading the reference's PNG directories and the ShapeNet reader stay
+out of scope.
 """
-import torch
-from torch.utils.data import TensorDataset
+import math
 
-from ..lie_tools import block_wigner_matrix_multiply, quaternions_to_eazyz, random_quaternions
+import torch
+from torch.utils.data import Dataset, TensorDataset
+
+from ..lie_tools import (block_wigner_matrix_multiply, quaternions_to_eazyz, random_group_matrices,
+                         random_quaternions, render_spherecube, rodrigues)
 
 
 def toy_harmonics(degrees=6, rep_copies=10, device=None):
@@ -58,3 +68,89 @@ class ToyDataset(TensorDataset):
     def save(self, path='data/toy.pt'):
         q, h, x = self.tensors
         torch.save((q.cpu(), h.cpu().contiguous(), x.cpu()), path)
+
+
+RENDER_CHUNK = 4096  # images in flight per render call while a dataset is generated
+
+
+def _render_chunked(g, size, samples):
+    """Images (n,3,size,size) of the poses g (n,3,3), at most RENDER_CHUNK per launch."""
+    return torch.cat([render_spherecube(g[i:i + RENDER_CHUNK], size=size, samples=samples)
+                      for i in range(0, max(g.shape[0], 1), RENDER_CHUNK)], 0)
+
+
+def spherecube_batch(n, device, generator=None, size=64, samples=2):
+    """A fresh batch for one training step: Haar poses g (n,3,3) and their images x
+    (n,3,size,size), both on ``device``.  Two draws and two kernels on the current stream; no
+    host read (``generator``: a torch.Generator of ``device``, default the device's stream)."""
+    g = random_group_matrices(n, device=device, generator=generator)
+    return g, render_spherecube(g, size=size, samples=samples)
+
+
+class SphereCubeDataset(Dataset):
+    """Items ``(0, group_el (3,3), image (3,size,size))`` as the reference's
+    SphereCubeDataset (datasets.py:87-92 over ShapeDataset.load_file), backed by the tensors
+    (g (n,3,3), x (n,3,size,size)) instead of a directory of PNGs."""
+    num_workers = 0
+    single_id = True
+    rgb = True
+
+    def __init__(self, tensors=None, device=None, path='data/spherecube.pt'):
+        if tensors is None:
+            tensors = torch.load(path, weights_only=True)
+        if device is not None:
+            tensors = [t.to(device) for t in tensors]
+        self.tensors = tuple(tensors)
+        g, x = self.tensors
+        assert g.shape[0] == x.shape[0] and tuple(g.shape[-2:]) == (3, 3), \
+            f"tensors must be (g (n,3,3), x (n,3,H,W)), got {tuple(g.shape)}, {tuple(x.shape)}"
+
+    @classmethod
+    def generate(cls, n=1000, size=64, device=None, generator=None, samples=2):
+        """n Haar poses (random_group_matrices) and their renders."""
+        g = random_group_matrices(n, device=device, generator=generator)
+        return cls(tensors=(g, _render_chunked(g, size, samples)))
+
+    def __len__(self):
+        return self.tensors[0].shape[0]
+
+    def __getitem__(self, idx):
+        g, x = self.tensors
+        return 0, g[idx], x[idx]
+
+    def save(self, path='data/spherecube.pt'):
+        torch.save(tuple(t.cpu() for t in self.tensors), path)
+
+    @staticmethod
+    def prep_batch(batch):
+        return batch
+
+
+class ScPairsDataset(SphereCubeDataset):
+    """Items ``(names (2,), gs (2,3,3), imgs (2,3,size,size))`` of two nearby poses, as the
+    reference's ScPairsDataset (datasets.py:95-127); tensors (g (num,2,3,3),
+    x (num,2,3,size,size)).  ``prep_batch`` flattens the pairs of a collated batch."""
+
+    def __init__(self, tensors=None, device=None, path='data/sc-pairs.pt'):
+        super().__init__(tensors, device, path)
+
+    @classmethod
+    def generate(cls, num=1000, step_size=2 * math.pi / 60, size=64, device=None, generator=None,
+                 samples=2):
+        """gen_spherecube_pairs.py:10-14: a Haar, b = a·rodrigues(randn·step_size)."""
+        a = random_group_matrices(num, device=device, generator=generator)
+        step = torch.randn(num, 3, device=device, generator=generator) * step_size
+        g = torch.stack([a, a.bmm(rodrigues(step))], 1)
+        x = _render_chunked(g.reshape(-1, 3, 3), size, samples)
+        return cls(tensors=(g, x.reshape(num, 2, *x.shape[1:])))
+
+    def __getitem__(self, idx):
+        g, x = self.tensors
+        return torch.zeros(2, dtype=torch.long), g[idx], x[idx]
+
+    def save(self, path='data/sc-pairs.pt'):
+        super().save(path)
+
+    @staticmethod
+    def prep_batch(batch):
+        return [t.view(-1, *t.shape[2:]) for t in batch]  # Flatten pairs

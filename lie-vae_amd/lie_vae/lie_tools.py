@@ -21,7 +21,7 @@ __all__ = [
     "quaternions_to_eazyz", "group_matrix_to_eazyz", "quaternions_to_group_matrix",
     "wigner_d_matrix", "block_wigner_matrix_multiply", "random_quaternions",
     "random_group_matrices", "so3_log", "geodesic_distance", "project_to_so3", "so3_mean",
-    "align_rotations",
+    "align_rotations", "render_spherecube",
 ]
 
 
@@ -130,6 +130,15 @@ def align_rotations(Z, G, side='both', weights=None, rounds=16):
     return _ops.align_rotations(Z, G, side=side, weights=weights, rounds=rounds)
 
 
+def render_spherecube(g, size=64, rgb=True, samples=2):
+    """Images (n, 3 | 1, size, size) of the sphere-cube scene seen from the camera frames g,
+    matrices (n,3,3) or scalar-last quaternions (n,4), rendered on g's device in one kernel
+    (include/lievae.h lv_render_spherecube_fwd; the scene: DESIGN.md §4.9).  ``g·Rz(φ)``
+    rotates the image in plane.  Forward only.  Extension: the reference reads these images
+    from files that Blender rendered."""
+    return _ops.render_spherecube(g, size=size, rgb=rgb, samples=samples)
+
+
 def group_matrix_to_quaternions(r):
     """Scalar-last quaternions — lie_tools.py:112-157."""
     assert list(r.shape[-2:]) == [3, 3], 'Input must be 3x3 matrices'
@@ -174,9 +183,10 @@ def block_wigner_matrix_multiply(angles, spectrum, max_degree, transpose=False):
     return _ops.group_action(angles, spectrum, max_degree, transpose=transpose)
 
 
-def random_quaternions(n, dtype=torch.float32, device=None):
-    """Haar-uniform quaternions (Shoemake) — lie_tools.py:256-263."""
-    u1, u2, u3 = torch.rand(3, n, dtype=dtype, device=device)
+def random_quaternions(n, dtype=torch.float32, device=None, generator=None):
+    """Haar-uniform quaternions (Shoemake) — lie_tools.py:256-263.  ``generator`` (extension):
+    a torch.Generator of ``device`` to draw from instead of the device's default stream."""
+    u1, u2, u3 = torch.rand(3, n, dtype=dtype, device=device, generator=generator)
     return torch.stack((
         torch.sqrt(1 - u1) * torch.sin(2 * np.pi * u2),
         torch.sqrt(1 - u1) * torch.cos(2 * np.pi * u2),
@@ -185,6 +195,6 @@ def random_quaternions(n, dtype=torch.float32, device=None):
     ), 1)
 
 
-def random_group_matrices(n, dtype=torch.float32, device=None):
+def random_group_matrices(n, dtype=torch.float32, device=None, generator=None):
     """lie_tools.py:266-267."""
-    return quaternions_to_group_matrix(random_quaternions(n, dtype, device))
+    return quaternions_to_group_matrix(random_quaternions(n, dtype, device, generator))
