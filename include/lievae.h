@@ -509,6 +509,54 @@ int lv_render_spherecube_fwd(const float* R, float* out, int64_t n, int size, in
 #define LV_RENDER_PLAN_LEN 4
 int lv_render_plan(int64_t n, int size, int channels, int samples, int flags, int64_t* plan);
 
+/* ---- triangle-mesh renderer (csrc/render_mesh.hip) --------------------------------------
+ * The images the reference's ShapeDataset reads from directories of rendered ShapeNet objects
+ * (experiments/datasets.py:18-85), rendered on the device from triangle meshes and poses
+ * instead.  Camera, sub-samples, light and shading are those of the
+ * sphere-cube renderer above, so the two are interchangeable; shading is flat with one albedo
+ * per triangle, and meshes are two-sided (a triangle seen from behind is lit on that side;
+ * nothing is culled by winding).
+ *
+ * Packing: verts (V,3) fp32, faces (T,3) int32, albedo (T,3) fp32 (clamped to [0, 1]) ->
+ * records (T,16) fp32, 16-byte aligned: v0, e1 = v1 - v0, e2 = v2 - v0, front rgb, back rgb,
+ * 0, with n = (e1 x e2)/|e1 x e2|, front = albedo (0.3 + 0.7 max(0, n.l)),
+ * back = albedo (0.3 + 0.7 max(0, -n.l)), l = (1,2,3)/sqrt(14).  A face index outside [0, V)
+ * is never used as an address: that triangle's record is all zeros (never hit) and
+ * *bad_counter (int32, device, zeroed by the caller) is incremented.  A triangle whose
+ * |e1 x e2| is zero, infinite or NaN gets zero edges and zero colours and is never hit.  T == 0 is a no-op.  V outside 0..(2^31-1)/3 or T
+ * outside 0..(2^31-1)/16 return LV_ERR_ARG. */
+int lv_mesh_pack(const float* verts, int64_t V, const int32_t* faces, const float* albedo,
+                 int64_t T, float* records, int32_t* bad_counter, void* stream);
+/* Rendering: R (n,3,3), mesh_id (n) int64 or NULL (every image shows mesh 0), records
+ * (total_records,16) holding K meshes back to back, ranges (K,2) int32 = (first record, count)
+ * per mesh, all on the device -> out (n, channels, size, size) fp32 in [0, 1].  A ray walks
+ * its mesh's triangles in index order (Moeller-Trumbore; the nearest hit wins, the lower index
+ * among equal distances; background 0).  An image whose id is outside [0, K), or whose range
+ * leaves [0, total_records), renders the background: no input can make the kernel read or
+ * write out of bounds, and every R and vertex, finite or not, gives a finite image.  One
+ * launch: runs of 4 pixels with float4 stores (size % 4 == 0 and a 16-byte aligned out) or of
+ * 1 pixel (otherwise, or with LV_MESH_SCALAR), the same bits.  max_blocks caps the grid below
+ * the default 65536 (0 = default); blocks stride over the remaining tiles.  Forward only.
+ * n < 0, size outside 1..1024, channels not 1 or 3, samples outside 1..4, K < 1,
+ * total_records outside 0..2^31-1, unknown flags, max_blocks < 0, a null or misaligned pointer
+ * with n > 0, or n * channels * size^2 * 4 beyond INT64_MAX return LV_ERR_ARG before any
+ * launch. */
+#define LV_MESH_SCALAR 1
+int lv_render_mesh_fwd(const float* R, const int64_t* mesh_id, const float* records,
+                       const int32_t* ranges, int K, int64_t total_records, float* out, int64_t n,
+                       int size, int channels, int samples, int flags, int64_t max_blocks,
+                       void* stream);
+/* Host-only: the checks and dispatch of the call above (for an aligned out), and, when
+ * host_ranges (K,2) is not NULL, a check of every range against total_records (a packer calls
+ * this before it accepts its ranges; LV_ERR_ARG names the first range that leaves the
+ * records).  plan[0] four-pixel path (1) or one-pixel (0), [1] grid blocks =
+ * min(cap, n * ceil(runs / 256)), cap = max_blocks if 0 < max_blocks < 65536 else 65536,
+ * [2] threads per block, [3] dynamic LDS bytes per block. */
+#define LV_RENDER_MESH_PLAN_LEN 4
+int lv_render_mesh_plan(const int32_t* host_ranges, int K, int64_t total_records, int64_t n,
+                        int size, int channels, int samples, int flags, int64_t max_blocks,
+                        int64_t* plan);
+
 #ifdef __cplusplus
 }
 #endif

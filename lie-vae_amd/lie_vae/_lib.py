@@ -106,6 +106,11 @@ LV_ROTATE_DIRECT = 1  # include/lievae.h
 _SIGS["lv_render_spherecube_fwd"] = [_P, _P, _I64, _I, _I, _I, _I, _P]
 _SIGS["lv_render_plan"] = [_I64, _I, _I, _I, _I, _P]
 LV_RENDER_SCALAR = 1  # include/lievae.h
+# triangle-mesh renderer (csrc/render_mesh.hip)
+_SIGS["lv_mesh_pack"] = [_P, _I64, _P, _P, _I64, _P, _P, _P]
+_SIGS["lv_render_mesh_fwd"] = [_P, _P, _P, _P, _I, _I64, _P, _I64, _I, _I, _I, _I, _I64, _P]
+_SIGS["lv_render_mesh_plan"] = [_P, _I, _I64, _I64, _I, _I, _I, _I, _I64, _P]
+LV_MESH_SCALAR = 1  # include/lievae.h
 LV_MOMENT_XT, LV_MOMENT_YT, LV_MOMENT_CT = 1, 2, 4  # include/lievae.h
 # vMF latent on S^3 (csrc/vmf.hip)
 _SIGS["lv_vmf_sample_fwd"] = [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]
@@ -233,6 +238,22 @@ def render_plan(n, size, channels, samples, flags=0):
     (include/lievae.h LV_RENDER_PLAN_LEN)."""
     buf = (ctypes.c_int64 * 4)()
     call("lv_render_plan", n, size, channels, samples, flags, buf)
+    return dict(zip(("wide", "blocks", "threads", "lds_bytes"), buf))
+
+
+def render_mesh_plan(n, size, channels, samples, flags=0, max_blocks=0, K=1, total_records=0,
+                     ranges=None):
+    """Host-only dispatch of lv_render_mesh_fwd as a dict; no GPU call (include/lievae.h
+    LV_RENDER_MESH_PLAN_LEN).  ``ranges``: K (first record, count) pairs on the host, checked
+    against ``total_records``."""
+    buf = (ctypes.c_int64 * 4)()
+    host = None
+    if ranges is not None:
+        flat = [int(v) for pair in ranges for v in pair]
+        assert len(flat) == 2 * K, f"ranges must hold K = {K} pairs"
+        host = (ctypes.c_int32 * len(flat))(*flat)
+    call("lv_render_mesh_plan", host, K, total_records, n, size, channels, samples, flags,
+         max_blocks, buf)
     return dict(zip(("wide", "blocks", "threads", "lds_bytes"), buf))
 
 

@@ -739,6 +739,48 @@ def render_spherecube(g, size=64, rgb=True, samples=2, flags=0):
     return out
 
 
+# ------------------------------------------------------ triangle-mesh renderer
+def mesh_pack(vertices, faces, albedo, records, bad_counter):
+    """One mesh into its slice of a record tensor (csrc/render_mesh.hip mesh_pack_k): vertices
+    (V,3) fp32, faces (T,3) int32, albedo (T,3) fp32 -> records (T,16) fp32 (a contiguous,
+    16-byte aligned view); ``bad_counter`` (one int32 element) counts the triangles with a
+    face index outside [0, V).  No host sync."""
+    _lib.require_device(vertices, faces, albedo, records, bad_counter)
+    V, T = vertices.shape[0], faces.shape[0]
+    assert vertices.dtype == F32 and vertices.is_contiguous() and tuple(vertices.shape) == (V, 3)
+    assert faces.dtype == torch.int32 and faces.is_contiguous() and tuple(faces.shape) == (T, 3)
+    assert albedo.dtype == F32 and albedo.is_contiguous() and tuple(albedo.shape) == (T, 3)
+    assert records.dtype == F32 and records.is_contiguous() and tuple(records.shape) == (T, 16)
+    assert bad_counter.dtype == torch.int32 and bad_counter.numel() == 1
+    call("lv_mesh_pack", ptr(vertices), V, ptr(faces), ptr(albedo), T, ptr(records),
+         ptr(bad_counter), _lib.stream_of(records.device))
+
+
+def render_mesh(g, meshes, mesh_id=None, size=64, rgb=True, samples=2, flags=0, max_blocks=0):
+    """Images of packed triangle meshes seen from the poses g (csrc/render_mesh.hip): g (n,3,3)
+    camera frames or (n,4) scalar-last quaternions, ``meshes`` a meshes.MeshSet on g's device,
+    ``mesh_id`` (n,) integers choosing each image's mesh (None: mesh 0; an id outside [0, K)
+    renders the background) -> (n, 3 | 1, size, size) fp32 in [0, 1].  One launch, no host
+    sync; forward only.  flags: _lib.LV_MESH_SCALAR forces the one-pixel path (same bits);
+    max_blocks caps the grid (0: the default cap)."""
+    quats = g.dim() == 2 and g.shape[1] == 4
+    assert quats or (g.dim() == 3 and tuple(g.shape[1:]) == (3, 3)), \
+        f"g must be matrices (n,3,3) or quaternions (n,4), got {tuple(g.shape)}"
+    _lib.require_device(g, meshes.records, mesh_id)
+    g = g.detach()
+    R = _f32c(unary(g, QUAT_TO_MAT) if quats else g)
+    n, C = R.shape[0], 3 if rgb else 1
+    if mesh_id is not None:
+        assert mesh_id.dim() == 1 and mesh_id.shape[0] == n and not mesh_id.is_floating_point(), \
+            f"mesh_id must be (n,) integers, got {tuple(mesh_id.shape)} {mesh_id.dtype}"
+        mesh_id = mesh_id.to(torch.int64).contiguous()
+    out = torch.empty((n, C, size, size), device=R.device, dtype=F32)
+    call("lv_render_mesh_fwd", ptr(R), ptr(mesh_id), ptr(meshes.records), ptr(meshes.ranges),
+         meshes.K, meshes.total_records, ptr(out), n, size, C, samples, flags, max_blocks,
+         _lib.stream_of(R.device))
+    return out
+
+
 class _EquivarianceDiff(torch.autograd.Function):
     """diffs[n] = sum (g_n enc_n - enc_rot_n)^2, g = s2s1rodrigues(e_x, cs) --
     losses/equivariance_loss.py:28-36.  cs carries no gradient (theta is drawn)."""

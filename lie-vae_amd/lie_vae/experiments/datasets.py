@@ -10,9 +10,14 @@ scene (csrc/render.hip), rendered on the device from the poses,
 reference's item layout ``(name, group_el, image)``.  ``spherecube_batch`` renders a fresh
 batch per training step.
 
+``MeshDataset`` is the reference's ShapeDataset (datasets.py:18-85: many objects, a per-object
+``name``, ``single_id = False``) with the images rendered on the device from triangle meshes
+(csrc/render_mesh.hip) instead of read from directories of rendered ShapeNet
+objects; ``mesh_batch`` renders a fresh batch per training step.
+
 All maps run in liblievae_hip.so, so every ``generate`` needs a GPU device (the product path
 has no CPU fallback).  Reading the reference's PNG directories and the ShapeNet reader stay
-out of scope.
+out of scope: MeshDataset takes its place for users who hold meshes.
 """
 import math
 
@@ -20,7 +25,8 @@ import torch
 from torch.utils.data import Dataset, TensorDataset
 
 from ..lie_tools import (block_wigner_matrix_multiply, quaternions_to_eazyz, random_group_matrices,
-                         random_quaternions, render_spherecube, rodrigues)
+                         random_quaternions, render_mesh, render_spherecube, rodrigues)
+from ..meshes import MeshSet
 
 
 def toy_harmonics(degrees=6, rep_copies=10, device=None):
@@ -154,3 +160,70 @@ class ScPairsDataset(SphereCubeDataset):
     @staticmethod
     def prep_batch(batch):
         return [t.view(-1, *t.shape[2:]) for t in batch]  # Flatten pairs
+
+
+def _mesh_set(meshes, device):
+    """``meshes`` as a MeshSet on ``device``: a MeshSet is taken as it is, a Mesh or a list of
+    Mesh is packed (the one host sync of mesh rendering)."""
+    return meshes if isinstance(meshes, MeshSet) else MeshSet(meshes, device)
+
+
+def _render_mesh_chunked(g, meshes, names, size, samples):
+    """Images (n,3,size,size) of mesh names[i] at pose g[i], at most RENDER_CHUNK per launch."""
+    return torch.cat([render_mesh(g[i:i + RENDER_CHUNK], meshes, names[i:i + RENDER_CHUNK],
+                                  size=size, samples=samples)
+                      for i in range(0, max(g.shape[0], 1), RENDER_CHUNK)], 0)
+
+
+def mesh_batch(n, device, meshes, generator=None, size=64, samples=2):
+    """A fresh batch for one training step: a uniformly random mesh per item (names (n,)
+    int64), Haar poses g (n,3,3) and the images x (n,3,size,size), all on ``device``.
+    ``meshes``: a MeshSet (then no host read happens here), a Mesh or a list of Mesh."""
+    meshes = _mesh_set(meshes, device)
+    names = torch.randint(meshes.K, (n,), device=device, generator=generator)
+    g = random_group_matrices(n, device=device, generator=generator)
+    return names, g, render_mesh(g, meshes, names, size=size, samples=samples)
+
+
+class MeshDataset(Dataset):
+    """Items ``(name, group_el (3,3), image (3,size,size))`` as the reference's ShapeDataset
+    (datasets.py:72-85), ``name`` the index of the item's mesh; backed by the tensors
+    (names (n,) int64, g (n,3,3), x (n,3,size,size))."""
+    num_workers = 0
+    single_id = False
+    rgb = True
+
+    def __init__(self, tensors=None, device=None, path='data/meshes.pt'):
+        if tensors is None:
+            tensors = torch.load(path, weights_only=True)
+        if device is not None:
+            tensors = [t.to(device) for t in tensors]
+        self.tensors = tuple(tensors)
+        names, g, x = self.tensors
+        assert names.dtype == torch.int64 and names.dim() == 1 and \
+            names.shape[0] == g.shape[0] == x.shape[0] and tuple(g.shape[-2:]) == (3, 3), \
+            "tensors must be (names (n,) int64, g (n,3,3), x (n,3,H,W)), got " \
+            f"{tuple(names.shape)} {names.dtype}, {tuple(g.shape)}, {tuple(x.shape)}"
+
+    @classmethod
+    def generate(cls, meshes, n=1000, size=64, device=None, generator=None, samples=2):
+        """n items: a uniformly random mesh of ``meshes`` each (drawn first), then n Haar poses
+        (random_group_matrices), then the renders."""
+        meshes = _mesh_set(meshes, device)
+        names = torch.randint(meshes.K, (n,), device=meshes.device, generator=generator)
+        g = random_group_matrices(n, device=meshes.device, generator=generator)
+        return cls(tensors=(names, g, _render_mesh_chunked(g, meshes, names, size, samples)))
+
+    def __len__(self):
+        return self.tensors[0].shape[0]
+
+    def __getitem__(self, idx):
+        names, g, x = self.tensors
+        return names[idx], g[idx], x[idx]
+
+    def save(self, path='data/meshes.pt'):
+        torch.save(tuple(t.cpu() for t in self.tensors), path)
+
+    @staticmethod
+    def prep_batch(batch):
+        return batch

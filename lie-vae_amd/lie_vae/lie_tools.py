@@ -21,7 +21,7 @@ __all__ = [
     "quaternions_to_eazyz", "group_matrix_to_eazyz", "quaternions_to_group_matrix",
     "wigner_d_matrix", "block_wigner_matrix_multiply", "random_quaternions",
     "random_group_matrices", "so3_log", "geodesic_distance", "project_to_so3", "so3_mean",
-    "align_rotations", "render_spherecube",
+    "align_rotations", "render_spherecube", "render_mesh",
 ]
 
 
@@ -137,6 +137,21 @@ def render_spherecube(g, size=64, rgb=True, samples=2):
     rotates the image in plane.  Forward only.  Extension: the reference reads these images
     from files that Blender rendered."""
     return _ops.render_spherecube(g, size=size, rgb=rgb, samples=samples)
+
+
+def render_mesh(g, meshes, mesh_id=None, size=64, rgb=True, samples=2):
+    """Images (n, 3 | 1, size, size) of triangle meshes seen from the camera frames g, matrices
+    (n,3,3) or scalar-last quaternions (n,4), rendered on g's device in one kernel
+    (include/lievae.h lv_render_mesh_fwd) with render_spherecube's camera and
+    light.  ``meshes``: a meshes.MeshSet on g's device, or a meshes.Mesh, which is packed on
+    the fly (a host sync; pack once into a MeshSet to avoid it).  ``mesh_id`` (n,) integers
+    picks each image's mesh (None: mesh 0; an id outside the set renders the background).
+    Forward only.  Extension: the reference reads such images from files."""
+    from .meshes import Mesh, MeshSet
+    if isinstance(meshes, Mesh):
+        _ops._lib.require_device(g)
+        meshes = MeshSet([meshes], g.device)
+    return _ops.render_mesh(g, meshes, mesh_id, size=size, rgb=rgb, samples=samples)
 
 
 def group_matrix_to_quaternions(r):
