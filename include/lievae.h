@@ -557,6 +557,61 @@ int lv_render_mesh_plan(const int32_t* host_ranges, int K, int64_t total_records
                         int size, int channels, int samples, int flags, int64_t max_blocks,
                         int64_t* plan);
 
+/* ---- spherical harmonics on S^2 (csrc/s2.hip) --------------------------------------------
+ * The signal behind the action decoder's spectrum (experiments/main.py:169, "the virtual
+ * signal on the Sphere"): f(x) = sum_k F_k Y_k(x), and the way back.  The reference
+ * has neither; the basis is the one its J tables belong to.  All fp32, L in 0..LV_MAX_DEGREE,
+ * M = (L+1)^2, C in 1..LV_MAX_CHANNELS.
+ *
+ * Basis: orthonormal real harmonics without the Condon-Shortley phase, flat index
+ * k = l^2 + l + m, m = -l..l, m < 0 sine-type and m > 0 cosine-type; Y_0 = 1/sqrt(4 pi) and
+ * degree 1 is sqrt(3/(4 pi)) (y, z, x).  Evaluated as Y_l^{+-m} = sqrt2 q_l^m(z) {Re, Im}(x+iy)^m
+ * with q_l^m a polynomial in z from a three-term recurrence in l: no trigonometric call, no
+ * division by sin(theta).  With g = Rz(a) Ry(b) Rz(c), Y_l(g x) = D_l(a, b, c) Y_l(x) for the D
+ * of lv_wigner_d_fwd, so synthesis(D(a) F, x) = synthesis(F, g^T x).
+ *
+ * Points x (P,3) need not be unit vectors: they are normalised in the kernel (first by the
+ * largest component, so no length overflows).  At +-z every m != 0 entry is exactly 0.  The
+ * zero vector and a point with a non-finite component have no direction: every harmonic of
+ * such a point is NaN (Y_0 too), hence its row of Y, its synthesis values, and -- a sum over
+ * all points -- every coefficient the analysis returns for a batch that has a value there.
+ * No address depends on a point's value.
+ *
+ * lv_s2_harmonics_fwd: x (P,3) -> Y (P,M).
+ * lv_s2_synthesis_fwd: values[b,p,c] = sum_k Y_k(x_p) F[b,k,c].  F (B,M,C) with F_batch_stride
+ * = M*C, or one shared (M,C) block with F_batch_stride = 0 (as lv_group_action_fwd takes its
+ * spectrum); x is shared by the batch; values (B,P,C).  Y stays in registers; the (M, tile)
+ * coefficient block of one batch element is staged once per block in LDS.  The two stride
+ * forms of the same spectrum give the same bits.
+ * lv_s2_analysis_fwd, the adjoint: F[b,k,c] = sum_p w_p Y_k(x_p) values[b,p,c]; w (P) or NULL
+ * (ones); values (B,P,C) -> F (B,M,C).  No atomics: one wave per partial sums its points in a
+ * fixed order into the workspace (lv_s2_analysis_workspace bytes), a second launch adds the
+ * partials in ascending order; the same inputs give the same bits on every run.
+ * B == 0 or P == 0 succeed and launch nothing (the analysis then leaves F unwritten: the
+ * caller zeroes an empty sum).  L or C outside their ranges, a negative count, an
+ * F_batch_stride other than 0 or M*C, a null pointer or a short workspace with a non-empty
+ * problem, and sizes whose byte offsets or grid leave the int64 / 2^31-1 block range return
+ * LV_ERR_ARG before any launch. */
+int lv_s2_harmonics_fwd(const float* x, float* Y, int64_t P, int L, void* stream);
+int lv_s2_synthesis_fwd(const float* F, int64_t F_batch_stride, const float* x, float* values,
+                        int64_t B, int64_t P, int L, int C, void* stream);
+size_t lv_s2_analysis_workspace(int64_t B, int64_t P, int L, int C);
+int lv_s2_analysis_fwd(const float* values, const float* x, const float* w, float* F, int64_t B,
+                       int64_t P, int L, int C, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* Host-only dispatch of the three calls above (B and C are ignored for the basis): plan[0]
+ * channels a lane accumulates (the channel tile: 1, 2, 4, 8 or 16; 0 for the basis), [1] grid
+ * blocks, [2] threads per block (synthesis: 64 while 256-thread blocks would number at most
+ * 512, else 256; analysis: 64, one wave per partial), [3] LDS bytes per block (the
+ * recurrence's tables, plus M * tile * 4 for the synthesis), [4] analysis: partial sums per
+ * coefficient = min(ceil(P / 64), ceil(2048 / (B * ceil(C / tile)))), a function of the shape
+ * alone, [5] analysis: blocks of the second launch. */
+#define LV_S2_OP_HARMONICS 0
+#define LV_S2_OP_SYNTHESIS 1
+#define LV_S2_OP_ANALYSIS 2
+#define LV_S2_PLAN_LEN 6
+int lv_s2_plan(int op, int64_t B, int64_t P, int L, int C, int64_t* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,12 @@ _SIGS["lv_mesh_pack"] = [_P, _I64, _P, _P, _I64, _P, _P, _P]
 _SIGS["lv_render_mesh_fwd"] = [_P, _P, _P, _P, _I, _I64, _P, _I64, _I, _I, _I, _I, _I64, _P]
 _SIGS["lv_render_mesh_plan"] = [_P, _I, _I64, _I64, _I, _I, _I, _I, _I64, _P]
 LV_MESH_SCALAR = 1  # include/lievae.h
+# spherical harmonics on S^2 (csrc/s2.hip)
+_SIGS["lv_s2_harmonics_fwd"] = [_P, _P, _I64, _I, _P]
+_SIGS["lv_s2_synthesis_fwd"] = [_P, _I64, _P, _P, _I64, _I64, _I, _I, _P]
+_SIGS["lv_s2_analysis_fwd"] = [_P, _P, _P, _P, _I64, _I64, _I, _I, _P, _SZ, _P]
+_SIGS["lv_s2_plan"] = [_I, _I64, _I64, _I, _I, _P]
+LV_S2_OP_HARMONICS, LV_S2_OP_SYNTHESIS, LV_S2_OP_ANALYSIS = 0, 1, 2  # include/lievae.h
 LV_MOMENT_XT, LV_MOMENT_YT, LV_MOMENT_CT = 1, 2, 4  # include/lievae.h
 # vMF latent on S^3 (csrc/vmf.hip)
 _SIGS["lv_vmf_sample_fwd"] = [_P, _P, _P, _P, _P, _I64, _I64, _I, _P]
@@ -120,13 +126,14 @@ _SIGS["lv_vmf_kl_bwd"] = [_P, _P, _P, _I64, _P]
 _SIGS["lv_vmf_log_prob_fwd"] = [_P, _P, _P, _P, _I64, _I64, _P]
 _SIGS["lv_vmf_log_prob_bwd"] = [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]
 _RESTYPES = {"lv_group_action_bwd_workspace": _SZ, "lv_last_error": ctypes.c_char_p,
-             "lv_so3_moment_workspace": _SZ,
+             "lv_so3_moment_workspace": _SZ, "lv_s2_analysis_workspace": _SZ,
              "lv_deconv4s2_packed_weight_elems": _SZ, "lv_deconv4s2_small_packed_weight_elems": _SZ,
              "lv_deconv4s2_packed_weight_elems_f32": _SZ,
              "lv_deconv4s2_small_dgrad_weight_elems": _SZ, "lv_deconv4s2_small_bwd_workspace_elems": _SZ,
              "lv_channel_sum_workspace_elems": _SZ, "lv_bn_workspace_elems": _SZ}
 _SIGS_EXTRA = {"lv_group_action_bwd_workspace": [_I64, _I, _I, _I],
                "lv_so3_moment_workspace": [_I64, _I], "lv_last_error": [],
+               "lv_s2_analysis_workspace": [_I64, _I64, _I, _I],
                "lv_deconv4s2_packed_weight_elems": [_I], "lv_deconv4s2_small_packed_weight_elems": [_I],
                "lv_deconv4s2_packed_weight_elems_f32": [_I],
                "lv_deconv4s2_small_dgrad_weight_elems": [_I],
@@ -255,6 +262,14 @@ def render_mesh_plan(n, size, channels, samples, flags=0, max_blocks=0, K=1, tot
     call("lv_render_mesh_plan", host, K, total_records, n, size, channels, samples, flags,
          max_blocks, buf)
     return dict(zip(("wide", "blocks", "threads", "lds_bytes"), buf))
+
+
+def s2_plan(op, B, P, L, C):
+    """Host-only dispatch of the S^2 kernels as a dict; no GPU call (include/lievae.h
+    LV_S2_PLAN_LEN).  op: LV_S2_OP_HARMONICS, _SYNTHESIS or _ANALYSIS."""
+    buf = (ctypes.c_int64 * 6)()
+    call("lv_s2_plan", op, B, P, L, C, buf)
+    return dict(zip(("tile", "blocks", "threads", "lds_bytes", "partials", "reduce_blocks"), buf))
 
 
 TORCH_OPS_PATH =os.environ.get("LIEVAE_TORCH_OPS_LIB", os.path.join(_HERE, "liblievae_torch.so"))

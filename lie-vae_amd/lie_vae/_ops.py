@@ -781,6 +781,124 @@ def render_mesh(g, meshes, mesh_id=None, size=64, rgb=True, samples=2, flags=0, 
     return out
 
 
+# ------------------------------------------------- spherical harmonics on S^2
+def _s2_points(x, what):
+    assert x.dim() == 2 and x.shape[1] == 3, f"{what}: x must be (P,3), got {tuple(x.shape)}"
+    return _f32c(x.detach())
+
+
+def s2_harmonics(x, L):
+    """x (P,3) -> Y (P,(L+1)^2), the real harmonics of csrc/s2.hip; forward only."""
+    x = _s2_points(x, "s2_harmonics")
+    _lib.require_device(x)
+    P = x.shape[0]
+    Y = torch.empty((P, (L + 1) ** 2), device=x.device, dtype=F32)
+    call("lv_s2_harmonics_fwd", ptr(x), ptr(Y), P, L, _lib.stream_of(x.device))
+    return Y
+
+
+def _s2_synthesis_raw(spec, x, L, scale=None):
+    """spec (M,C) or (B,M,C), x (P,3), both fp32 contiguous -> (P,C) or (B,P,C); `scale` (P)
+    multiplies the rows of the result (the analysis VJP)."""
+    shared = spec.dim() == 2
+    B, C, P = (1 if shared else spec.shape[0]), spec.shape[-1], x.shape[0]
+    out = torch.empty((B, P, C), device=spec.device, dtype=F32)
+    call("lv_s2_synthesis_fwd", ptr(spec), 0 if shared else spec.shape[1] * C, ptr(x), ptr(out),
+         B, P, L, C, _lib.stream_of(spec.device))
+    if scale is not None:
+        out = out * scale[None, :, None]
+    return out[0] if shared else out
+
+
+def _s2_analysis_raw(values, x, w, L):
+    """values (P,C) or (B,P,C), x (P,3), w (P) or None, all fp32 contiguous -> (M,C) or
+    (B,M,C)."""
+    shared = values.dim() == 2
+    B, P, C = (1 if shared else values.shape[0]), values.shape[-2], values.shape[-1]
+    M = (L + 1) ** 2
+    dev = values.device
+    if P == 0:  # the empty sum; nothing is launched
+        F = torch.zeros((B, M, C), device=dev, dtype=F32)
+    else:
+        F = torch.empty((B, M, C), device=dev, dtype=F32)
+        nb = int(_lib.load().lv_s2_analysis_workspace(B, P, L, C))
+        ws = torch.empty(max(nb, 8), device=dev, dtype=torch.uint8)
+        call("lv_s2_analysis_fwd", ptr(values), ptr(x), ptr(w), ptr(F), B, P, L, C, ptr(ws), nb,
+             _lib.stream_of(dev))
+    return F[0] if shared else F
+
+
+class _S2Synthesis(torch.autograd.Function):
+    """values = Y(x) spectrum; the VJP in the spectrum is the analysis kernel with unit
+    weights.  A shared (M,C) spectrum comes back as (P,C)."""
+
+    @staticmethod
+    def forward(ctx, spec, x, L):
+        ctx.save_for_backward(x)
+        ctx.L = L
+        return _s2_synthesis_raw(spec, x, L)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return _s2_analysis_raw(_f32c(g), x, None, ctx.L), None, None
+
+
+class _S2Analysis(torch.autograd.Function):
+    """spectrum = Y(x)^T diag(w) values; the VJP in the values is the synthesis kernel, its rows
+    scaled by w."""
+
+    @staticmethod
+    def forward(ctx, values, x, w, L):
+        ctx.save_for_backward(x, w)
+        ctx.L = L
+        return _s2_analysis_raw(values, x, w, L)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        return _s2_synthesis_raw(_f32c(g), x, ctx.L, scale=w), None, None, None
+
+
+def _s2_degrees(rows, what):
+    L = int(round(rows ** 0.5)) - 1
+    assert L >= 0 and (L + 1) ** 2 == rows, f"{what}: spectrum rows {rows} != (L+1)^2"
+    return L
+
+
+def s2_synthesis(spectrum, x):
+    """spectrum (M,C), (B,M,C) or a stride-0 expand of (M,C); x (P,3) shared by the batch ->
+    (P,C) for a shared spectrum, else (B,P,C).  Differentiable in the spectrum only."""
+    assert spectrum.dim() in (2, 3), \
+        f"s2_synthesis: spectrum must be (M,C) or (B,M,C), got {tuple(spectrum.shape)}"
+    L = _s2_degrees(spectrum.shape[-2], "s2_synthesis")
+    x = _s2_points(x, "s2_synthesis")
+    _lib.require_device(spectrum, x)
+    expand = None
+    if spectrum.dim() == 3 and spectrum.stride(0) == 0:
+        # (M,C) passed once; autograd routes the gradient through the views back to the block
+        expand = spectrum.shape[0]
+        spectrum = spectrum.as_strided(spectrum.shape[1:], spectrum.stride()[1:])
+    out = _S2Synthesis.apply(_contig(spectrum), x, L)
+    return out if expand is None else out.expand(expand, -1, -1)
+
+
+def s2_analysis(values, x, weights, L):
+    """values (P,C) or (B,P,C), x (P,3), weights (P) or None -> (M,C) or (B,M,C).
+    Differentiable in the values only."""
+    assert values.dim() in (2, 3), \
+        f"s2_analysis: values must be (P,C) or (B,P,C), got {tuple(values.shape)}"
+    x = _s2_points(x, "s2_analysis")
+    P = x.shape[0]
+    assert values.shape[-2] == P, f"s2_analysis: values rows {values.shape[-2]} != points {P}"
+    assert weights is None or tuple(weights.shape) == (P,), \
+        f"s2_analysis: weights must be ({P},), got {tuple(weights.shape)}"
+    _lib.require_device(values, x, weights)
+    if weights is not None:
+        weights = _f32c(weights.detach())
+    return _S2Analysis.apply(_contig(values), x, weights, L)
+
+
 class _EquivarianceDiff(torch.autograd.Function):
     """diffs[n] = sum (g_n enc_n - enc_rot_n)^2, g = s2s1rodrigues(e_x, cs) --
     losses/equivariance_loss.py:28-36.  cs carries no gradient (theta is drawn)."""

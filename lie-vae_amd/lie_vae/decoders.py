@@ -50,6 +50,17 @@ class ActionNet(nn.Module):
         out = _ops.fused_exp_action(mu, v, self.item_rep, self.degrees, transpose=self.transpose)
         return out.view(-1, self.matrix_dims * self.rep_copies)
 
+    def signal(self, x, angles=None):
+        """Extension: the decoder's signal on the sphere, f(x) = sum_k item_rep[k] Y_k(x)
+        (lie_vae/s2.py), at the points x (P,3) -> (P, rep_copies).  With ``angles`` (n,3) the
+        signal after the action, (n, P, rep_copies): ``harmonics`` followed by the synthesis,
+        so ``self.transpose`` is honoured.  Differentiable in item_rep and the angles, not in
+        the points."""
+        if angles is None:
+            return _ops.s2_synthesis(self.item_rep, x)
+        spec = self.harmonics(angles).view(-1, self.matrix_dims, self.rep_copies)
+        return _ops.s2_synthesis(spec, x)
+
     def forward(self, angles, z_content=None):
         item = self.harmonics(angles)
         if self.mlp:

@@ -52,14 +52,23 @@ class ToyDataset(TensorDataset):
         super().__init__(*tensors)
 
     @classmethod
-    def generate(cls, n=1000, degrees=6, rep_copies=10, device=None, batch_size=64):
+    def generate(cls, n=1000, degrees=6, rep_copies=10, device=None, batch_size=64,
+                 harmonics=None):
         """datasets.py:143-158: seed 0, spectrum first, then one Haar batch of poses per
-        ``batch_size`` chunk, each pushed through the fused ZYZ + Wigner-D action."""
+        ``batch_size`` chunk, each pushed through the fused ZYZ + Wigner-D action.
+        ``harmonics`` (extension): a given ((degrees+1)^2, rep_copies) spectrum, e.g. of
+        ``lie_vae.s2.project``, instead of the random draw; the poses then follow the seed
+        directly."""
         # One seed, then spectrum and every pose batch from the same device stream, in the
         # reference's order (datasets.py:144-151): torch.manual_seed(0) seeds the CPU and
         # every CUDA generator, exactly like the reference's manual_seed + cuda.manual_seed.
         torch.manual_seed(0)
-        harmonics = toy_harmonics(degrees, rep_copies, device)
+        if harmonics is None:
+            harmonics = toy_harmonics(degrees, rep_copies, device)
+        else:
+            assert tuple(harmonics.shape) == ((degrees + 1) ** 2, rep_copies), \
+                f"harmonics must be ({(degrees + 1) ** 2},{rep_copies}), got {tuple(harmonics.shape)}"
+            harmonics = harmonics.detach().to(device=device, dtype=torch.float32)
         xs, qs = [], []
         for i in range(0, n, batch_size):
             batch_n = min(i + batch_size, n) - i
