@@ -322,6 +322,16 @@ int lv_so3_log_posterior_fwd(const float* v, const float* sigma, float* out, int
                              int64_t B, int k, void* stream);
 int lv_so3_log_posterior_bwd(const float* v, const float* sigma, const float* gout, float* gv,
                              float* gsigma, int64_t ns, int64_t B, int k, void* stream);
+/* Host-only dispatch of the two entries above (no GPU call; refuses the same sizes and k).
+ * k must lie in [0, 64].  Two kernels per direction: a wave per element (lane t holds wrapped
+ * term t - k) and a thread per element (the 2k+1 terms in a loop).  The forward takes the
+ * wave kernel when k <= 31 and 0 < ns*B <= 65536; the backward works per b (it sums gsigma
+ * over s) and takes the wave kernel when k <= 31 and 0 < B <= 65536, ns > 0; otherwise the
+ * thread kernel.  ns == 0: the backward only zeroes gsigma (v, gout, gv may be null).
+ * plan[0] fwd_wave, [1] bwd_wave, [2] fwd_blocks, [3] bwd_blocks (0: nothing launched),
+ * [4] threads per block. */
+#define LV_SO3_LOG_POSTERIOR_PLAN_LEN 5
+int lv_so3_log_posterior_plan(int64_t ns, int64_t B, int k, int64_t* plan);
 
 /* ---- Sreparameterize, the vMF latent on S^3: reparameterize.py:58-97 (csrc/vmf.hip) -----
  * Latent modes vmf / vmfq.  m = 4 only.  mu (B,4) unit vectors, kappa (B) > 0 (the module

@@ -384,6 +384,13 @@ constexpr float kHalfLog2Pi = 0.9189385332046727f;  // log(sqrt(2 pi))
 
 constexpr int kMaxWrap = 64;
 
+// Volume term of wrapped angle thk (reparameterize.py:255-259), both clamps.
+__device__ __forceinline__ float logpost_vol(float thk) {
+  const float th2 = fmaxf(thk * thk, 1e-3f);
+  const float den = fmaxf(2.f - 2.f * cosf(thk), 1e-3f);
+  return logf(th2 / den);
+}
+
 // One wrapped term l_t of the density (reparameterize.py:240-260), logs of sigma hoisted.
 __device__ __forceinline__ float logpost_term(int t, float th, const float u[3],
                                               const float var[3], const float logsig[3]) {
@@ -395,19 +402,49 @@ __device__ __forceinline__ float logpost_term(int t, float th, const float u[3],
     const float term = (-(x * x) / (2.f * var[j]) - logsig[j]) - kHalfLog2Pi;
     lp = (j == 0) ? term : lp + term;
   }
-  const float th2 = fmaxf(thk * thk, 1e-3f);
-  const float den = fmaxf(2.f - 2.f * cosf(thk), 1e-3f);
-  return lp + logf(th2 / den);
+  return lp + logpost_vol(thk);
 }
 
-// max-shifted logsumexp over t = -k..k (lie_vae/utils.py:4-26), two passes.
-__device__ __forceinline__ float logpost_lse(float th, const float u[3], const float var[3],
-                                             const float logsig[3], int k) {
-  float m = -INFINITY;
+// max-shifted logsumexp over t = -k..k (lie_vae/utils.py:4-26), two passes: the largest
+// term m and sum_t exp(l_t - m); the value is m + log(sum).
+__device__ __forceinline__ void logpost_max_sum(float th, const float u[3], const float var[3],
+                                                const float logsig[3], int k, float& m,
+                                                float& sum) {
+  m = -INFINITY;
   for (int t = -k; t <= k; ++t) m = fmaxf(m, logpost_term(t, th, u, var, logsig));
-  float sum = 0.f;
+  sum = 0.f;
   for (int t = -k; t <= k; ++t) sum += expf(logpost_term(t, th, u, var, logsig) - m);
-  return m + logf(sum);
+}
+
+// The backward's weight of term t is softmax_t = exp(l_t - m) / sum, as autograd forms it for
+// the reference's logsumexp: never exp(l_t - lse).  lse = m + log(sum) is rounded to fp32, so at
+// a narrow sigma (|lse| ~ 1e4, half an ulp 5e-4) every weight of the sample, and with it gv
+// and gsigma, would be off by up to 5e-4 relative.
+//
+// The weights see only differences of terms, and the Gaussian part of a term, -q thk^2 / 2 with
+// q = sum_j (u_j / sigma_j)^2, reaches 1e3..1e4 at a narrow sigma: its fp32 roundings (and that
+// of theta = |v| itself) move a difference by ~1e-4.  Where two terms carry weight with
+// opposite slopes (theta near pi: t = 0 and t = -1 at +-pi, slopes -+theta q) that is 1e-4 of
+// the whole gradient.  So the backward takes the Gaussian part in fp64 from the fp32 inputs:
+// three divisions and a square root per sample, one multiply-add per term, no fp64
+// transcendental; -log sigma_j and the constant are common to all t and drop out.  The volume
+// part, of order 1, stays fp32.
+struct LogpostWide {
+  double th, q;  // |v|; sum_j (v_j / sigma_j)^2 / |v|^2
+};
+__device__ __forceinline__ LogpostWide logpost_wide(const float a[3], const float sg[3]) {
+  LogpostWide p;
+  const double a0 = a[0], a1 = a[1], a2 = a[2];
+  const double r0 = a0 / (double)sg[0], r1 = a1 / (double)sg[1], r2 = a2 / (double)sg[2];
+  const double n2 = a0 * a0 + a1 * a1 + a2 * a2;
+  p.th = sqrt(n2);
+  p.q = (r0 * r0 + r1 * r1 + r2 * r2) / n2;
+  return p;
+}
+// l_t up to the terms common to all t; th is the fp32 angle the volume term is taken at.
+__device__ __forceinline__ double logpost_term_wide(int t, const LogpostWide& p, float th) {
+  const double thk = p.th + (double)t * 6.283185307179586;
+  return -0.5 * p.q * thk * thk + (double)logpost_vol(th + (float)t * kTwoPi);
 }
 
 __global__ void so3_logpost_fwd_k(const float* v, const float* sigma, float* out, int64_t ns,
@@ -420,7 +457,9 @@ __global__ void so3_logpost_fwd_k(const float* v, const float* sigma, float* out
     for (int j = 0; j < 3; ++j) { var[j] = sg[j] * sg[j]; ls[j] = logf(sg[j]); }
     const float th = norm3(a);
     const float u[3] = {a[0] / th, a[1] / th, a[2] / th};
-    out[i] = logpost_lse(th, u, var, ls, k);
+    float m, sum;
+    logpost_max_sum(th, u, var, ls, k, m, sum);
+    out[i] = m + logf(sum);
   }
 }
 
@@ -437,11 +476,15 @@ __global__ void so3_logpost_bwd_k(const float* v, const float* sigma, const floa
       ld(v + i * 3, a);
       const float th = norm3(a);
       const float u[3] = {a[0] / th, a[1] / th, a[2] / th};
-      const float lse = logpost_lse(th, u, var, ls, k);
-      const float g = gout[i];
+      const LogpostWide wd = logpost_wide(a, sg);
+      double m = -INFINITY;
+      for (int t = -k; t <= k; ++t) m = fmax(m, logpost_term_wide(t, wd, th));
+      float sum = 0.f;
+      for (int t = -k; t <= k; ++t) sum += expf((float)(logpost_term_wide(t, wd, th) - m));
+      const float g = gout[i] / sum;
       float gth = 0.f, gu[3] = {0.f, 0.f, 0.f};
       for (int t = -k; t <= k; ++t) {
-        const float w = g * expf(logpost_term(t, th, u, var, ls) - lse);
+        const float w = g * expf((float)(logpost_term_wide(t, wd, th) - m));
         const float thk = th + (float)t * kTwoPi;
         float dth = 0.f;
 #pragma unroll
@@ -475,6 +518,11 @@ constexpr int64_t kWaveMaxElems = 1 << 16;  // beyond: enough elements to fill t
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+  return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o));
   return x;
 }
 __device__ __forceinline__ float wave_sum(float x) {
@@ -522,12 +570,14 @@ __global__ void so3_logpost_bwd_wave_k(const float* v, const float* sigma, const
       ld(v + i * 3, a);
       const float th = norm3(a);
       const float u[3] = {a[0] / th, a[1] / th, a[2] / th};
-      const float term = on ? logpost_term(t, th, u, var, ls) : -INFINITY;
-      const float m = wave_max(term);
-      const float lse = m + logf(wave_sum(on ? expf(term - m) : 0.f));
+      const LogpostWide wd = logpost_wide(a, sg);
+      const double term = on ? logpost_term_wide(t, wd, th) : (double)-INFINITY;
+      const double m = wave_max(term);
+      const float e = on ? expf((float)(term - m)) : 0.f;
+      const float sum = wave_sum(e);
       float gth = 0.f, gu[3] = {0.f, 0.f, 0.f};
       if (on) {
-        const float w = gout[i] * expf(term - lse);
+        const float w = gout[i] * (e / sum);
         const float thk = th + (float)t * kTwoPi;
         float dth = 0.f;
 #pragma unroll
@@ -561,6 +611,22 @@ inline dim3 grid_for_waves(int64_t nwaves) {
   int64_t b = (nwaves * 64 + kBlock - 1) / kBlock;
   if (b > 65536) b = 65536;
   return dim3((unsigned)b);
+}
+
+// Sizes and k shared by lv_so3_log_posterior_fwd / _bwd / _plan.
+int logpost_check(int64_t ns, int64_t B, int k) {
+  LV_CHECK_ARG(ns >= 0 && B >= 0, "bad sizes");
+  LV_CHECK_ARG(k >= 0 && k <= kMaxWrap, "k must be in [0, %d]", kMaxWrap);
+  return LV_OK;
+}
+// The dispatch of the density, one rule per direction (the entry points and the plan call
+// these): the forward has ns * B elements, the backward one element per b (it sums over s).
+inline bool logpost_fwd_wave(int64_t ns, int64_t B, int k) {
+  const int64_t n = ns * B;
+  return n > 0 && k <= kWaveMaxK && n <= kWaveMaxElems;
+}
+inline bool logpost_bwd_wave(int64_t ns, int64_t B, int k) {
+  return ns > 0 && B > 0 && k <= kWaveMaxK && B <= kWaveMaxElems;
 }
 
 }  // namespace lv
@@ -808,10 +874,9 @@ int lv_n0_sample_bwd(const float* eps, const float* gv, float* gsigma, int64_t n
 int lv_so3_log_posterior_fwd(const float* v, const float* sigma, float* out, int64_t ns,
                              int64_t B, int k, void* stream) {
   const int64_t n = ns * B;
-  LV_CHECK_ARG(ns >= 0 && B >= 0, "bad sizes");
-  LV_CHECK_ARG(k >= 0 && k <= kMaxWrap, "k must be in [0, %d]", kMaxWrap);
+  if (int rc = logpost_check(ns, B, k)) return rc;
   LV_PTRS(v && sigma && out);
-  if (n > 0 && k <= kWaveMaxK && n <= kWaveMaxElems) {
+  if (logpost_fwd_wave(ns, B, k)) {
     clear_error();
     hipLaunchKernelGGL(so3_logpost_fwd_wave_k, grid_for_waves(n), dim3(kBlock), 0,
                        (hipStream_t)stream, v, sigma, out, ns, B, k);
@@ -822,20 +887,35 @@ int lv_so3_log_posterior_fwd(const float* v, const float* sigma, float* out, int
 int lv_so3_log_posterior_bwd(const float* v, const float* sigma, const float* gout, float* gv,
                              float* gsigma, int64_t ns, int64_t B, int k, void* stream) {
   const int64_t n = B;
-  LV_CHECK_ARG(ns >= 0 && B >= 0, "bad sizes");
-  LV_CHECK_ARG(k >= 0 && k <= kMaxWrap, "k must be in [0, %d]", kMaxWrap);
-  LV_PTRS(v && sigma && gout && gv && gsigma);
+  if (int rc = logpost_check(ns, B, k)) return rc;
+  // ns == 0: v, gout and gv are empty (null from an empty tensor); gsigma is a sum of nothing
+  LV_CHECK_ARG(n == 0 || (sigma && gsigma && (ns == 0 || (v && gout && gv))),
+               "null pointer argument");
   if (ns == 0) {
-    (void)hipMemsetAsync(gsigma, 0, sizeof(float) * 3 * B, (hipStream_t)stream);
+    clear_error();
+    if (B > 0) (void)hipMemsetAsync(gsigma, 0, sizeof(float) * 3 * B, (hipStream_t)stream);
     return LV_OK;
   }
-  if (n > 0 && k <= kWaveMaxK && n <= kWaveMaxElems) {
+  if (logpost_bwd_wave(ns, B, k)) {
     clear_error();
     hipLaunchKernelGGL(so3_logpost_bwd_wave_k, grid_for_waves(n), dim3(kBlock), 0,
                        (hipStream_t)stream, v, sigma, gout, gv, gsigma, ns, B, k);
     LV_RETURN_LAUNCH("so3_logpost_bwd_wave_k");
   }
   LV_LAUNCH1(so3_logpost_bwd_k, n, v, sigma, gout, gv, gsigma, ns, B, k);
+}
+int lv_so3_log_posterior_plan(int64_t ns, int64_t B, int k, int64_t* plan) {
+  clear_error();
+  LV_CHECK_ARG(plan, "null pointer argument");
+  if (int rc = logpost_check(ns, B, k)) return rc;
+  const bool fw = logpost_fwd_wave(ns, B, k), bw = logpost_bwd_wave(ns, B, k);
+  const int64_t nf = ns * B, nb = ns > 0 ? B : 0;  // ns == 0: the backward is a memset
+  plan[0] = fw;
+  plan[1] = bw;
+  plan[2] = nf == 0 ? 0 : (fw ? grid_for_waves(nf) : grid_for(nf)).x;
+  plan[3] = nb == 0 ? 0 : (bw ? grid_for_waves(nb) : grid_for(nb)).x;
+  plan[4] = kBlock;
+  return LV_OK;
 }
 
 }  // extern "C"

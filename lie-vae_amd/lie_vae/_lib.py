@@ -60,6 +60,7 @@ _SIGS = {
     "lv_n0_sample_bwd": [_P, _P, _P, _I64, _I64, _P],
     "lv_so3_log_posterior_fwd": [_P, _P, _P, _I64, _I64, _I, _P],
     "lv_so3_log_posterior_bwd": [_P, _P, _P, _P, _P, _I64, _I64, _I, _P],
+    "lv_so3_log_posterior_plan": [_I64, _I64, _I, _P],
     "lv_so3_log_fwd": [_P, _P, _I64, _P],
     "lv_so3_log_bwd": [_P, _P, _P, _I64, _P],
     "lv_so3_rel_log_fwd": [_P, _P, _P, _I64, _I64, _P],
@@ -238,6 +239,14 @@ def rotate_plan(N, C, H, W, flags=0):
     buf = (ctypes.c_int64 * 4)()
     call("lv_rotate_plan", N, C, H, W, flags, buf)
     return dict(zip(("staged", "blocks", "threads", "lds_bytes"), buf))
+
+
+def so3_log_posterior_plan(ns, B, k):
+    """Host-only dispatch of lv_so3_log_posterior_fwd / _bwd as a dict; no GPU call
+    (include/lievae.h LV_SO3_LOG_POSTERIOR_PLAN_LEN)."""
+    buf = (ctypes.c_int64 * 5)()
+    call("lv_so3_log_posterior_plan", ns, B, k, buf)
+    return dict(zip(("fwd_wave", "bwd_wave", "fwd_blocks", "bwd_blocks", "threads"), buf))
 
 
 def render_plan(n, size, channels, samples, flags=0):
