@@ -111,16 +111,10 @@ __global__ __launch_bounds__(256) void action_bwd_reduce5_vjp_kernel(const float
 
 namespace {
 
-template <int... Ls>
-constexpr std::array<int, sizeof...(Ls)> nnz_table(std::integer_sequence<int, Ls...>) {
-  return {j_nnz<Ls>()...};
-}
-constexpr auto kNnz = nnz_table(std::make_integer_sequence<int, LV_MAX_DEGREE + 1>{});
-
-// Lane-instruction cost of one degree of the chain (FMA-pairs + loads + staging).
+// Lane-instruction cost of one degree of the chain (FMA-pairs + loads + staging; the
+// forward's: chain_degree_cost, action_fwd.h, over the kNnz table there).
 inline double degree_cost(int l, bool bwd) {
-  const int n = 2 * l + 1;
-  const double fwd = 2.0 * kNnz[l] + 6.0 * n + 3.0 * n;
+  const double fwd = chain_degree_cost(l);
   return bwd ? 2.2 * fwd : fwd;
 }
 
@@ -232,9 +226,8 @@ constexpr size_t kTileMaxLds = 80 * 1024;    // >= 2 blocks per CU
 // box: profiles/r06_ab_nseg_sweep.txt): <= 4 groups per CU 7 waves (batch 4,096: 6.92 us
 // against 7.12-7.17 at 6), <= 16 8 waves (8,192: 11.5 vs 12.0; 16,384: 17.6 vs 19.5 at 4),
 // beyond 4 waves (65,536: 60.3 vs 62.3-65.1 at 6-8; 32,768 flat from 4 to 8).
-constexpr double kTileSegCostFew = 300.0;    // -> 7 waves at l = 10
-constexpr double kTileSegCostMid = 260.0;    // -> 8
-constexpr double kTileSegCostLarge = 560.0;  // -> 4
+// (kTileSegCostFew / Mid / Large = 300 / 260 / 560 -> 7 / 8 / 4 waves at l = 10: action_fwd.h,
+// with tile_waves and tile_min_waves, the bound the kernel compiles its one-wave code by)
 constexpr int64_t kTileFewGroupsPerCU = 4, kTileMidGroupsPerCU = 16;
 constexpr int kTileClasses = 0;              // block priority classes at <= kTileFewGroupsPerCU: off (plan_tile)
 constexpr double kTilePrologue = 60.0;      // per-wave fixed cost: spectrum slice, multiples reads
@@ -306,12 +299,12 @@ bool plan_tile(FwdLaunch& p, int L, int out_bytes, int cus) {
   int Sw = 64 / a.C;
   if (a.C == kTileFastC && kEnvSw >= 2 && kEnvSw < Sw) Sw = kEnvSw;
   const int64_t groups = (a.n + Sw - 1) / Sw;
-  double total = 0.0;
-  for (int l = 0; l <= L; ++l) total += degree_cost(l, false);
   const double target = groups <= kTileFewGroupsPerCU * cus   ? kTileSegCostFew
                         : groups <= kTileMidGroupsPerCU * cus ? kTileSegCostMid
                                                               : kTileSegCostLarge;
-  int nseg = std::max(1, std::min(std::min(8, L + 1), (int)std::ceil(total / target)));
+  // ceil(total chain cost / target) within [1, min(8, L + 1)]; never below tile_min_waves(L),
+  // which the product's kernel relies on (no one-wave code from l_max = 6)
+  int nseg = tile_waves(L, target);
   if (kEnvTileNseg > 0) nseg = std::min(std::min(8, L + 1), kEnvTileNseg);
   // the prologue takes one thread per (sample, slot): 3*Sw threads of the block
   nseg = std::min(L + 1, std::max(nseg, (3 * Sw + 63) / 64));
@@ -936,6 +929,23 @@ int lv_ab_fwd_chain(int fused, int64_t F_batch_stride, int out_dtype, int64_t n,
   info[2] = (int)offsetof(ActionArgs, chain_fetch);
   info[3] = tile_vgpr_ceiling(L);
   for (int l = 0; l <= LV_MAX_DEGREE; ++l) info[4 + l] = l <= L ? chain_depth(L, l) : -1;
+  return LV_OK;
+}
+
+// Wave counts of the forward tile kernel's plans (A/B build, host only): info[0]
+// tile_min_waves(L), the fewest waves a product plan gives a block at this l_max; [1] 1 if
+// the product's mu-free fused kernel of this l_max holds the angle maths behind its prologue
+// barrier, the one-wave block's placement (only where [0] is 1); [2..4] tile_waves(L, target)
+// of the few / mid / large batch classes (kTileSegCost*).  info holds 5 ints.
+int lv_ab_fwd_min_waves(int L, int* info) {
+  clear_error();
+  LV_CHECK_ARG(info, "null info");
+  LV_CHECK_ARG(L >= 0 && L <= LV_MAX_DEGREE, "l_max must be in [0, %d] (got %d)", LV_MAX_DEGREE, L);
+  info[0] = tile_min_waves(L);
+  info[1] = tile_min_waves(L) == 1 ? 1 : 0;
+  info[2] = tile_waves(L, kTileSegCostFew);
+  info[3] = tile_waves(L, kTileSegCostMid);
+  info[4] = tile_waves(L, kTileSegCostLarge);
   return LV_OK;
 }
 

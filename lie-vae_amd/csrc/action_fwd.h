@@ -1,5 +1,7 @@
 #pragma once
+#include <array>
 #include <type_traits>
+#include <utility>
 // Forward group-action kernels for gfx950 (MI355X) + their launchers.
 // Instantiated once per l_max in action_inst.hip (-DLV_INST_L=k) so the 21 degree
 // variants compile in parallel; host planning lives in action.hip.
@@ -295,6 +297,44 @@ constexpr int chain_depth(int LT, int l) {
 static_assert(chain_depth(10, 10) == kChainDepthFull && chain_depth(20, 20) == kChainDepthOff,
               "chain depth: config 2 prefetches its top degree, config 5's top degree has no room");
 
+// The planner's per-wave chain cost targets (plan_tile, action.hip, which documents the
+// measurements behind them) and the wave count they give -- here, next to the kernel, because
+// the kernel compiles out what no plan of its l_max can reach (tile_min_waves).
+constexpr double kTileSegCostFew = 300.0;    // -> 7 waves at l = 10
+constexpr double kTileSegCostMid = 260.0;    // -> 8
+constexpr double kTileSegCostLarge = 560.0;  // -> 4
+constexpr int kTileMaxWaves = 8;
+template <int... Ls>
+constexpr std::array<int, sizeof...(Ls)> nnz_table(std::integer_sequence<int, Ls...>) {
+  return {j_nnz<Ls>()...};
+}
+constexpr auto kNnz = nnz_table(std::make_integer_sequence<int, LV_MAX_DEGREE + 1>{});
+// Lane-instruction cost of one degree of the forward chain (FMA-pairs + loads + staging).
+constexpr double chain_degree_cost(int l) { return 2.0 * kNnz[l] + 6.0 * (2 * l + 1) + 3.0 * (2 * l + 1); }
+constexpr double chain_total_cost(int L) {
+  double total = 0.0;
+  for (int l = 0; l <= L; ++l) total += chain_degree_cost(l);
+  return total;
+}
+// waves per block for a per-wave cost target: ceil(total / target) within [1, min(8, L + 1)]
+constexpr int tile_waves(int L, double target) {
+  const double total = chain_total_cost(L);
+  int k = (int)(total / target);
+  if (k * target < total) ++k;
+  const int cap = kTileMaxWaves < L + 1 ? kTileMaxWaves : L + 1;
+  return k < 1 ? 1 : (k > cap ? cap : k);
+}
+// The fewest waves any product plan gives a block of the l_max = L kernel, whatever the batch
+// and the channel count: the wave count of the largest cost target.  (The prologue's thread
+// count only raises a plan's count, and the product does not read the A/B knobs.)
+constexpr int tile_min_waves(int L) {
+  const double t = kTileSegCostFew > kTileSegCostMid ? kTileSegCostFew : kTileSegCostMid;
+  return tile_waves(L, t > kTileSegCostLarge ? t : kTileSegCostLarge);
+}
+static_assert(tile_min_waves(5) == 1 && tile_min_waves(6) == 2 && tile_min_waves(8) == 3 &&
+                  tile_min_waves(10) == 4 && tile_waves(10, kTileSegCostFew) == 7,
+              "tile plan: one-wave blocks up to l_max = 5; config 2 runs 7 waves, l = 10 never fewer than 4");
+
 // Tile kernel.  One block = one sample group (Sw = 64 / C samples, one wave's lanes) x
 // nseg degree segments, one wave per segment.
 //   1. Prologue ONCE per (sample j, Euler slot q): the block's first 3*Sw threads each
@@ -427,12 +467,21 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   // barrier but puts ~550 wave-instructions on the VALU-bound chain: 6.74-6.77 us against
   // 6.65-6.68 at config 2 (profiles/r07_ab_startup_c2.txt), so 0 stays.  A one-wave block
   // always writes behind the barrier.
+  // The product's kernel holds that second copy -- ~300 instructions at the chain's first
+  // address, which every wave branches over -- only where a product plan of this l_max can
+  // have a one-wave block (kMinWaves, tile_min_waves: up to l_max = 5); beyond, the angle
+  // waves' indices are constants too wherever every plan has them (wave 1 from two waves,
+  // l_max >= 6; wave 2 from three, l_max >= 8).  The A/B library, whose knobs force wave
+  // counts and placement 1, keeps all of it.  Measured at config 2: DESIGN.md section 9, "The
+  // one-wave code out of the kernels that never run one wave".
+  constexpr int kMinWaves = kAbKnobs ? 1 : tile_min_waves(LT);
   constexpr bool kAngLate = FUSED && !MAYMU;
-  const int ang_wave = nw > 1 ? 1 : 0;
-  const int beta_wave = nw > 2 ? 2 : ang_wave;
+  constexpr bool kAngBehind = kAngLate && kMinWaves == 1;
+  const int ang_wave = (kMinWaves > 1 || nw > 1) ? 1 : 0;
+  const int beta_wave = (kMinWaves > 2 || nw > 2) ? 2 : ang_wave;
   const bool ang_on = kAngLate && aang != nullptr && lane < Sv;
   const bool dirs_lane = ang_on && wave == ang_wave, beta_lane = ang_on && wave == beta_wave;
-  const bool ang_early = ang_order == 0 && nw > 1;
+  const bool ang_early = !kAngBehind || (ang_order == 0 && nw > 1);
   float vang[3] = {0.f, 0.f, 0.f};
   if (dirs_lane || beta_lane) load3(lane, vang);
   auto write_ang = [&]() {
@@ -559,7 +608,7 @@ __device__ __forceinline__ void fwd_tile_body(const ActionArgs& a, int64_t grp) 
   if (cprio == 2) __builtin_amdgcn_s_setprio(2);
   else if (cprio == 1) __builtin_amdgcn_s_setprio(1);
   else if (prio >= 2) __builtin_amdgcn_s_setprio(0);
-  if constexpr (kAngLate) {
+  if constexpr (kAngBehind) {
     if ((dirs_lane || beta_lane) && !ang_early) write_ang();
   }
   OutT* st_lane = reinterpret_cast<OutT*>(stage_b) + j * MC + c;
@@ -729,6 +778,10 @@ template <int LT>
 int FwdLauncher<LT>::run(FwdLaunch& p) {
   const bool bf16 = p.dtype == LV_DTYPE_BF16;
   if (p.tile) {
+    if (!kAbKnobs && p.gy < tile_min_waves(LT)) {  // the kernel holds no code for such a block
+      set_error("tile plan of %d waves below the kernel's minimum %d at l_max %d", p.gy, tile_min_waves(LT), LT);
+      return LV_ERR_ARG;
+    }
     if (p.a.C == kTileFastC)
       launch_tile<kTileFastC>(p, bf16);
     else

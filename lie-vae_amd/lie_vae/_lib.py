@@ -147,7 +147,8 @@ EXPORTED = sorted(list(_SIGS) + list(_SIGS_EXTRA))
 # bound when the loaded library has them, never part of the product header
 _SIGS_AB = {"lv_deconv4s2_fwd_bf16_tile": [_P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, _P],
             "lv_ab_fwd_classes": [_I, _I64, _I, _I64, _I, _I, _I, _P],
-            "lv_ab_fwd_chain": [_I, _I64, _I, _I64, _I, _I, _I, _P]}
+            "lv_ab_fwd_chain": [_I, _I64, _I, _I64, _I, _I, _I, _P],
+            "lv_ab_fwd_min_waves": [_I, _P]}
 
 _lib = None
 
@@ -231,6 +232,19 @@ def fwd_chain(fused, F_batch_stride, out_dtype, n, L, C, cus=0):
     d = dict(zip(("tile", "chain_fetch", "off_chain_fetch", "vgpr_ceiling"), buf[:4]))
     d["depths"] = [x for x in buf[4:] if x >= 0]
     return d
+
+
+def fwd_min_waves(L):
+    """Wave counts of the forward tile kernel's plans at l_max L as a dict (A/B library only;
+    action.hip lv_ab_fwd_min_waves); no GPU call.  min_waves: the fewest waves a product plan
+    gives a block; late_angles: 1 if the product's mu-free fused kernel holds the angle maths
+    behind its prologue barrier (a one-wave block's placement); few / mid / large: the waves of
+    the three batch classes."""
+    if not hasattr(load(), "lv_ab_fwd_min_waves"):
+        raise LieVaeHipError("lv_ab_fwd_min_waves: an entry of the A/B library (liblievae_hip_ab.so)")
+    buf = (ctypes.c_int * 5)()
+    call("lv_ab_fwd_min_waves", L, buf)
+    return dict(zip(("min_waves", "late_angles", "few", "mid", "large"), buf))
 
 
 def rotate_plan(N, C, H, W, flags=0):
